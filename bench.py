@@ -19,7 +19,7 @@ The triples of `--bucket` consecutive steps are all-reduced as ONE message (fewe
 collectives: a 24-byte all-reduce is pure latency), asynchronously to the launch streams, which
 keep simulating; every bucket is waited for inside the timed region.
 Before the W warm-up steps the same kernel runs untimed for --preheat-ms (clock ramp; reported).
-The timed region of exactly K steps is repeated --regions (5) times back to back, each bracketed by
+The timed region of exactly K steps is repeated --regions (default 1) times back to back, each bracketed by
 barrier + torch.cuda.synchronize() on both sides with the MAX over ranks taken; ms_per_step, value
 and timed_region_s are the MEDIAN region's (min / max / all regions reported beside them).  At N > 1
 over RCCL the barrier that closes a region is the all-reduce of its last bucket of triples (an
@@ -866,15 +866,27 @@ def compact_line(detail, detail_name="bench_detail.json"):
     return line
 
 
+def dump_outputs(mc, out_dir, triple, disc, settings, inputs, X):
+    """What a caller of the timed path receives from one step: the (sum, sum2, n) triple the launch writes and the
+    price closed from it.  Inputs, seed and path ranges are fixed by the arguments, so two builds compare output for output."""
+    import numpy as np
+    price, ci = mc.closing(triple[0], triple[1], int(triple[2]), disc)
+    if settings.get("control_variate"):
+        price += disc * mc.basket_control_mean(inputs, X)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "triple.npy"), np.asarray(triple, dtype=np.float64))
+    np.save(os.path.join(out_dir, "estimate.npy"), np.asarray([price, ci], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--regions", type=int, default=1,
                     help="the K-step timed region is repeated this many times back to back (fresh path ranges each time, one "
                          "pre-heat before the first); ms_per_step and value are the MEDIAN region's, min and max are reported: a "
-                         "20-step region is 1 ms, one sample of it moves by +-4 %% between runs")
+                         "20-step region is 1 ms, one sample of it moves by +-4 %% between runs.  Default 1: exactly K timed steps")
     ap.add_argument("--workload", default="vanilla_f32")
     ap.add_argument("--paths", type=int, default=0, help="paths per GPU per step (default: the workload's)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
@@ -937,6 +949,9 @@ def main():
                          "torch.cuda.synchronize().  barrier: that all-reduce, then a separate dist.barrier(), then the synchronize")
     ap.add_argument("--bucket", type=int, default=25,
                     help="steps whose triples share one all-reduce (bucketed collective: 24 B x bucket); 1 = one per step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last timed step to DIR/*.npy (float64): "
+                         "triple.npy = the all-reduced (sum, sum2, n) triple, estimate.npy = (price, 95 %% half-width) closed from it")
     args = ap.parse_args()
 
     # the host driver of these boxes supports dmabuf IPC only: without this RCCL's communicator set-up between processes fails with
@@ -1085,7 +1100,7 @@ def main():
     for i in range(W):
         step(i)
     drain()
-    eng.profile(1 if R * K < 100 else args.profile_every)   # short runs: every launch of the first context is sampled
+    eng.profile(1 if K < 20 else args.profile_every)   # short regions: every launch of the first context is sampled
     # R timed regions of exactly K steps each, back to back: barrier + synchronize, K steps, drain, barrier + synchronize,
     # MAX over ranks -- the contract's bracket, repeated.  ms_per_step / value come from the MEDIAN region.
     region_s, host_sides = [], []
@@ -1211,6 +1226,8 @@ def main():
         if settings.get("control_variate"):     # the simulated quantity is payoff - control: its closed-form mean comes back on the host
             price += disc * mc.basket_control_mean(inputs, X)
         assert int(tot[2]) == R * K * step_total, (tot[2], R * K * step_total)
+        if args.dump_outputs:
+            dump_outputs(mc, args.dump_outputs, triples[W + R * K - 1].cpu().tolist(), disc, settings, inputs, X)
         units_per_step = step_total
         value = units_per_step * K / elapsed
         # ---- roofline of the dominant kernel (the simulation kernel) -------------------------------------------

@@ -3,6 +3,7 @@ include/mc_mi355x.h declares, the legacy libraries export the reference's three 
 and include/MonteCarlo.h has the reference's struct layouts (measured with gcc on
 the reference header: dp 40/192/16/72, sp 20/96/8/36 for N=3)."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
+REF_ROOT = os.environ.get("MC_REFERENCE", "/root/reference")    # the reference tree, where it is mounted
 
 
 @pytest.fixture(scope="module")
@@ -101,22 +103,22 @@ def test_dropin_header_layout(tmp_path, key):
 
 
 def test_layout_matches_live_reference_header(tmp_path):
-    """Where the reference is mounted, compile the same probe against ITS header and compare."""
-    ref = "/root/reference/double_precision"
-    if not os.path.isdir(ref):
-        pytest.skip("reference not mounted")
+    """The same probe against OUR header gives what it printed against the reference's (tests/golden/ref_layout.json); where the
+    reference is mounted, its header is probed live as well and must still print the recorded bytes."""
     src = tmp_path / "layout.c"
     src.write_text(LAYOUT_C)
-    outs = []
-    for inc, flags in ((ref, []), (INC, [])), (("/root/reference/single_precision", []), (INC, ["-DMC_SINGLE_PRECISION"])):
-        pair = []
-        for i, f in (inc, flags):
-            exe = tmp_path / "p"
-            subprocess.check_call(["gcc", "-w", f"-I{i}", str(src), "-o", str(exe)] + f)
-            pair.append(subprocess.check_output([str(exe)]))
-        outs.append(pair)
-    for a, b in outs:
-        assert a == b
+    exe = tmp_path / "p"
+
+    def probe(inc, flags):
+        subprocess.check_call(["gcc", "-w", f"-I{inc}", str(src), "-o", str(exe)] + flags)
+        return subprocess.check_output([str(exe)]).decode()
+    with open(os.path.join(ROOT, "tests", "golden", "ref_layout.json")) as f:
+        recorded = json.load(f)
+    for sub, flags in (("double_precision", []), ("single_precision", ["-DMC_SINGLE_PRECISION"])):
+        assert probe(INC, flags) == recorded[sub], sub
+        ref = os.path.join(REF_ROOT, sub)
+        if os.path.isdir(ref):
+            assert probe(ref, []) == recorded[sub], sub
 
 
 def test_no_gpu_is_a_loud_error(mc):

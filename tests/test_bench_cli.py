@@ -10,8 +10,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_help_renders_and_names_the_contract_flags():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--regions", "--strong-reps"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--regions", "--strong-reps", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_dump_outputs_writes_the_triple_and_its_price(tmp_path):
+    """--dump-outputs: the last timed step's (sum, sum2, n) and the price closed from it, float64, by the library's own closing."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import montecarlocuda_amd as mc
+    triple = [1.0386e9, 2.51e11, 10 ** 8]
+    disc = float(np.exp(-0.048790))
+    bench.dump_outputs(mc, str(tmp_path / "out"), triple, disc, {}, bench.VAN, "f32")
+    assert sorted(os.listdir(tmp_path / "out")) == ["estimate.npy", "triple.npy"]
+    tri, est = np.load(tmp_path / "out" / "triple.npy"), np.load(tmp_path / "out" / "estimate.npy")
+    assert tri.dtype == np.float64 and tri.tolist() == triple
+    assert est.dtype == np.float64 and est.tolist() == list(mc.closing(*triple, disc))
+    assert 9 < est[0] < 11 and 0 < est[1] < 0.01
 
 
 # ---- the ONE stdout line: at most 4096 bytes, whatever the run measured (round 4's had grown to 32 KB: BENCH_r04 parsed null) ----

@@ -96,10 +96,10 @@ def test_survey_known_answers(po):
 
 # ---- live comparison with the compiled reference, extra seeds ---------------------------
 @pytest.mark.parametrize("X", ["f64", "f32"])
-def test_live_reference_extra_seeds(po, X):
-    if not po.ref_available(X, 3):
-        pytest.skip("oracle/_ref not built here")
-    ref = po.Ref(X, 3)
+def test_live_reference_extra_seeds(po, ref, X):
+    """Other seeds and market data than ref_mc.json holds: the compiled reference live where it is built, else its recorded
+    answers (tests/golden/ref_live.json)."""
+    ref = ref(X, 3)
     opt = dict(s=105.0, k=95.0, r=0.02, v=0.35, t=2.5)
     for seed in (3, 99, 2024):
         e, ci = ref.vanilla(opt, 5000, seed)
@@ -121,7 +121,7 @@ def test_live_reference_extra_seeds(po, X):
         assert (r["expected"], r["confidence"]) == (e, ci)
 
 
-def test_factor_from_cov_bitwise(po):
+def test_factor_from_cov_bitwise(po, ref):
     """Covariance input: normalise to vols + correlation, then the reference's Chol.  The golden
     correlation and factor come from numpy scalars of the target precision and the compiled reference Chol
     (tests/golden/gen_golden_cov.py); the oracle twin must reproduce v, the correlation and the factor bit for bit."""
@@ -135,22 +135,20 @@ def test_factor_from_cov_bitwise(po):
         assert (corr.astype(np.float64) == np.array([[fromhex(x) for x in row] for row in c["corr"]])).all(), key
         assert (a.astype(np.float64) == np.array([[fromhex(x) for x in row] for row in c["a"]])).all(), key
         assert bad == c["bad_pivots"], key
-    # live against the compiled reference where it is present
-    if po.ref_available("f64", 4):
-        rng = np.random.default_rng(5)
-        for X in ("f64", "f32"):
-            g = rng.standard_normal((4, 9)) * 0.2
-            v, corr, a, bad = po.factor_from_cov(X, g @ g.T)
-            assert (po.Ref(X, 4).chol(corr.tolist()) == a).all() and bad == 0
+    # against the compiled reference (live where it is built, else its recorded answers)
+    rng = np.random.default_rng(5)
+    for X in ("f64", "f32"):
+        g = rng.standard_normal((4, 9)) * 0.2
+        v, corr, a, bad = po.factor_from_cov(X, g @ g.T)
+        assert (ref(X, 4).chol(corr.tolist()) == a).all() and bad == 0
 
 
-def test_reference_at_O0_gives_the_same_bits(po):
+def test_reference_at_O0_gives_the_same_bits(po, ref):
     """The reference's own Makefile builds the host file without -O (Makefile:157,252-253); the goldens were produced at
     -O2 -ffp-contract=off.  Where the compiled reference is present, its -O0 build must return the same bits (SURVEY 8c
-    "Determinism") -- bench.py times that build as the -O0 footnote of the CPU baseline."""
-    if not po.ref_available("f64", 3, "_O0"):
-        pytest.skip("oracle/_ref -O0 build not present")
+    "Determinism") -- bench.py times that build as the -O0 footnote of the CPU baseline.  Live where that build is present, else
+    its recorded answers."""
     for c in load_golden("ref_mc.json")["cases"]:
         if c["kind"] == "vanilla" and c["paths"] <= 100000:
-            e, ci = po.Ref(c["X"], 3, "_O0").vanilla(c["opt"], c["paths"], c["seed"])
+            e, ci = ref(c["X"], 3, "_O0").vanilla(c["opt"], c["paths"], c["seed"])
             assert (e, ci) == (fromhex(c["expected"]), fromhex(c["confidence"])), c
