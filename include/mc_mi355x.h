@@ -327,6 +327,31 @@ int mc_basket_greeks_lr_run_f32(mc_context *ctx, const mc_basket_f32 *opt, uint6
 int mc_basket_greeks_lr_run_f64(mc_context *ctx, const mc_basket_f64 *opt, uint64_t seed, uint64_t first_path,
                                 uint64_t n_paths, mc_result *price, mc_result *delta, mc_result *vega);
 
+/* ---- second-order Greeks of the vanilla and basket calls ---------------------------------------------
+ * The mixed estimator (Glasserman 7.3): the likelihood-ratio derivative of the pathwise delta, so no indicator is
+ * differentiated twice.  Same stream and path indexing as the first-order Greeks; plain estimator, Philox with native normals
+ * only (antithetic, XORWOW, MC_NORMALS_F32 on the _f64 entry points, and for the basket the control variate: MC_ERR_UNSUPPORTED);
+ * needs v > 0 and t > 0 (MC_ERR_INVALID).
+ * Vanilla, one pass, z the path's normal, I = [S_T > K]:
+ *   gamma = d2V/dS2        = I S_T / S^2 (z / (sigma sqrt T) - 1)
+ *   vanna = d2V/dS dsigma  = I S_T / S ((z^2 - 1) / sigma - z sqrt T)
+ * discounted means with their own 95 % half-widths; price, delta and vega are the same bits as mc_vanilla_greeks_run_*'s. */
+typedef struct { mc_result price, delta, vega, gamma, vanna; } mc_vanilla_greeks2;
+int mc_vanilla_greeks2_run_f32(mc_context *ctx, const mc_option_f32 *opt, uint64_t seed,
+                               uint64_t first_path, uint64_t n_paths, mc_vanilla_greeks2 *out);
+int mc_vanilla_greeks2_run_f64(mc_context *ctx, const mc_option_f64 *opt, uint64_t seed,
+                               uint64_t first_path, uint64_t n_paths, mc_vanilla_greeks2 *out);
+/* Basket: the symmetric n x n gamma matrix d2V / dS_a dS_b.  With I = [B > K], p_a = I w_a S_a(T) / S_a (the pathwise delta term),
+ * y = L^-T g (the LR basket Greeks' whitened normals) and c_b = 1 / (S_b v_b sqrt T):
+ *   gamma[a][b] = 1/2 (p_a y_b c_b + p_b y_a c_a) - [a == b] p_a / S_a
+ * discounted, each entry with its own half-width.  gamma is a caller array of n*n results, row-major, both triangles filled (the
+ * kernel computes the n (n + 1) / 2 entries a <= b, one pass over the paths per 4 x 4 tile of them); price is the same bits as
+ * mc_basket_greeks_run_*'s.  Inputs as for mc_basket_greeks_lr_run_*: t > 0, every v[a] > 0, a non-singular factor. */
+int mc_basket_gamma_run_f32(mc_context *ctx, const mc_basket_f32 *opt, uint64_t seed, uint64_t first_path,
+                            uint64_t n_paths, mc_result *price, mc_result *gamma);
+int mc_basket_gamma_run_f64(mc_context *ctx, const mc_basket_f64 *opt, uint64_t seed, uint64_t first_path,
+                            uint64_t n_paths, mc_result *price, mc_result *gamma);
+
 /* ---- CVA with its pathwise delta and vega -------------------------------------------------
  * On the CVA kernel's stream (reference loop dp/MonteCarloKernel.cu:241-262), not discounted, like the CVA itself (:466):
  *   d CVA / d S_0   = LGD sum_j dp_j cnd(d1_j) S_j / S_0

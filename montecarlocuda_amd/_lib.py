@@ -70,6 +70,10 @@ class Greeks(C.Structure):
     _fields_ = [("price", Result), ("delta", Result), ("vega", Result)]
 
 
+class Greeks2(C.Structure):
+    _fields_ = [("price", Result), ("delta", Result), ("vega", Result), ("gamma", Result), ("vanna", Result)]
+
+
 class CvaGreeks(C.Structure):
     _fields_ = [("cva", Result), ("delta", Result), ("vega", Result)]
 
@@ -93,6 +97,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_{_p}_run_grid_{_x}" for _p in ("vanilla", "basket", "cva")]       # the reference's launch geometry
     EXPORTS += [f"mc_vanilla_greeks_run_{_x}", f"mc_vanilla_greeks_lr_run_{_x}", f"mc_basket_greeks_run_{_x}", f"mc_cva_greeks_run_{_x}",
                 f"mc_basket_greeks_lr_run_{_x}", f"mc_cva_greeks_lr_run_{_x}"]
+    EXPORTS += [f"mc_vanilla_greeks2_run_{_x}", f"mc_basket_gamma_run_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -162,6 +167,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_basket_greeks_lr_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result),
                                                                C.POINTER(Result)]
         getattr(L, f"mc_cva_greeks_lr_run_{X}").argtypes = [ctx, C.POINTER(CVA[X]), u64, u64, u64, C.POINTER(CvaGreeks)]
+        getattr(L, f"mc_vanilla_greeks2_run_{X}").argtypes = [ctx, C.POINTER(OPTION[X]), u64, u64, u64, C.POINTER(Greeks2)]
+        getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 
 

@@ -1122,6 +1122,8 @@ static int planes_run(mc_context *c, size_t real_bytes, int planes, int grid_y, 
     int pairs = 0;
     for (const Segment &s : segs)
         pairs += grid_for(c->blocks, s.count);
+    if ((uint64_t)pairs * (uint64_t)grid_y > UINT32_MAX)   // the tickets of the call's arrivals are 32-bit
+        return fail(MC_ERR_INVALID, "greeks: %d workgroups x %d passes do not fit in one call; use fewer blocks", pairs, grid_y);
     Tail t = make_tail(c, pairs, 1.0, 1.0, n, c->g_triples, planes, 2 * c->blocks + 2);
     t.partials = c->g_pairs;
     if (c->fused)
@@ -1155,6 +1157,21 @@ static int planes_run(mc_context *c, size_t real_bytes, int planes, int grid_y, 
     return MC_OK;
 }
 
+// the pricing paths' exponent-range guards (VanillaTraits<>::prepare): refuse inputs whose terminal spot overflows the
+// simulation type instead of returning inf/NaN sums with MC_OK
+template <class Real, class In>
+static int greeks_spot_in_range(const In *o)
+{
+    const double drift = ((double)o->r - 0.5 * (double)o->v * (double)o->v) * (double)o->t;
+    const double vol = (double)o->v * std::sqrt((double)o->t);
+    const bool ok = sizeof(Real) == 4 ? std::fabs(std::ceil((drift + vol * 6.77) * 1.4426950408889634074)) < 100 &&
+                                            std::fabs(drift - vol * 6.77) * 1.4426950408889634074 < 100
+                                      : exponent_in_range(std::fabs(drift) + vol * Z_MAX_F64);
+    if (!ok)
+        return fail(MC_ERR_INVALID, "greeks: (r - v^2/2) t and v sqrt(t) put the terminal spot outside the range of the simulation type");
+    return MC_OK;
+}
+
 template <class Real, class In, class Opt, bool LR>
 static int greeks_run(mc_context *c, const In *o, uint64_t seed, uint64_t first, uint64_t n, mc_vanilla_greeks *out)
 {
@@ -1165,16 +1182,7 @@ static int greeks_run(mc_context *c, const In *o, uint64_t seed, uint64_t first,
         return fail(MC_ERR_INVALID, "likelihood-ratio greeks: need v>0 and t>0 (the scores divide by sigma sqrt t)");
     if (c->antithetic)
         return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
-    {   // the pricing paths' exponent-range guards (VanillaTraits<>::prepare): refuse inputs whose terminal spot
-        // overflows the simulation type instead of returning inf/NaN sums with MC_OK
-        const double drift = ((double)o->r - 0.5 * (double)o->v * (double)o->v) * (double)o->t;
-        const double vol = (double)o->v * std::sqrt((double)o->t);
-        const bool ok = sizeof(Real) == 4 ? std::fabs(std::ceil((drift + vol * 6.77) * 1.4426950408889634074)) < 100 &&
-                                                std::fabs(drift - vol * 6.77) * 1.4426950408889634074 < 100
-                                          : exponent_in_range(std::fabs(drift) + vol * Z_MAX_F64);
-        if (!ok)
-            return fail(MC_ERR_INVALID, "greeks: (r - v^2/2) t and v sqrt(t) put the terminal spot outside the range of the simulation type");
-    }
+    if (int rc = greeks_spot_in_range<Real>(o)) return rc;
     constexpr uint64_t NPB = GenPhilox::npb<Real>();
     Opt k;
     greeks_prepare(*o, k);
@@ -1205,6 +1213,41 @@ extern "C" int mc_vanilla_greeks_lr_run_f64(mc_context *c, const mc_option_f64 *
                                             mc_vanilla_greeks *out)
 {
     return greeks_run<double, mc_option_f64, GreeksF64, true>(c, o, seed, first, n, out);
+}
+
+// second order (vanilla_greeks2_kernel): price, delta, vega, gamma, vanna.  The inputs' checks are the likelihood-ratio
+// Greeks' (the gamma and vanna scores divide by sigma sqrt t)
+template <class Real, class In, class Opt>
+static int greeks2_run(mc_context *c, const In *o, uint64_t seed, uint64_t first, uint64_t n, mc_vanilla_greeks2 *out)
+{
+    if (int rc = check_common(c, o, first, n, out)) return rc;
+    if (!finite_pos(o->s) || !std::isfinite((double)o->k) || !(o->v >= 0) || !(o->t >= 0) || !std::isfinite((double)o->r))
+        return fail(MC_ERR_INVALID, "vanilla: need s>0, finite k, v>=0, t>=0, finite r");
+    if (!((double)o->v > 0 && (double)o->t > 0))
+        return fail(MC_ERR_INVALID, "second-order greeks: need v>0 and t>0 (the scores divide by sigma sqrt t)");
+    if (c->antithetic)
+        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
+    if (int rc = greeks_spot_in_range<Real>(o)) return rc;
+    constexpr uint64_t NPB = GenPhilox::npb<Real>();
+    Opt k;
+    greeks_prepare(*o, k);
+    const Real inv_spot = (Real)(1.0 / (double)o->s);
+    const uint64_t end = first + n, u0 = first / NPB, u1 = (end + NPB - 1) / NPB;
+    mc_result *r[5] = {&out->price, &out->delta, &out->vega, &out->gamma, &out->vanna};
+    return planes_run(c, sizeof(Real), 5, 1, u0, u1 - u0, n, std::exp(-(double)o->r * (double)o->t), r,
+                      [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
+                          vanilla_greeks2_kernel<Opt, Real><<<g, GROUP, 0, st>>>(t, k, make_work(seed, s, first, end), inv_spot);
+                      });
+}
+extern "C" int mc_vanilla_greeks2_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                          mc_vanilla_greeks2 *out)
+{
+    return greeks2_run<float, mc_option_f32, GreeksF32>(c, o, seed, first, n, out);
+}
+extern "C" int mc_vanilla_greeks2_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                          mc_vanilla_greeks2 *out)
+{
+    return greeks2_run<double, mc_option_f64, GreeksF64>(c, o, seed, first, n, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1775,13 +1818,10 @@ static int cva_enqueue(mc_context *c, const typename CvaIn<Real>::type *v, uint6
 // ---------------------------------------------------------------------------------------
 // Greeks of the basket call and of the CVA: secondary kernels, plain estimator, synchronous
 // ---------------------------------------------------------------------------------------
+// the inputs' checks and the constant table of basket_greeks_kernel (and, LR = true, of basket_gamma_kernel), uploaded
 template <class Real, bool LR>
-static int basket_greeks_run(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first, uint64_t n,
-                             mc_result *price, mc_result *delta, mc_result *vega)
+static int basket_greeks_setup(mc_context *c, const typename BasketIn<Real>::type *o, BasketGreeks<Real> &k)
 {
-    if (int rc = check_common(c, o, first, n, price)) return rc;
-    if (!delta || !vega)
-        return fail(MC_ERR_INVALID, "basket greeks: NULL output array");
     if (o->n < 1 || o->n > MC_MAX_ASSETS_GENERIC)
         return fail(MC_ERR_UNSUPPORTED, "basket: n=%d outside the supported range 1..%d", o->n, MC_MAX_ASSETS_GENERIC);
     if (!o->s || !o->v || !o->p || !o->d || !o->w)
@@ -1848,11 +1888,23 @@ static int basket_greeks_run(mc_context *c, const typename BasketIn<Real>::type 
     key[bytes + 1] = LR ? 'R' : 'G';
     if (int rc = begin_call(c, c->stream)) return rc;
     if (int rc = upload_table(c, c->stream, key, host.data(), bytes)) return rc;
-    BasketGreeks<Real> k;
     k.consts = (const Real *)c->d_table;
     k.n = na;
     k.strike = o->k;
     k.sqrt_t = (Real)sqrt_t;
+    return MC_OK;
+}
+
+template <class Real, bool LR>
+static int basket_greeks_run(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first, uint64_t n,
+                             mc_result *price, mc_result *delta, mc_result *vega)
+{
+    if (int rc = check_common(c, o, first, n, price)) return rc;
+    if (!delta || !vega)
+        return fail(MC_ERR_INVALID, "basket greeks: NULL output array");
+    BasketGreeks<Real> k;
+    if (int rc = basket_greeks_setup<Real, LR>(c, o, k)) return rc;
+    const int na = o->n;
     constexpr int NPB = GenPhilox::npb<Real>();
     const size_t lds = (size_t)((na + NPB - 1) / NPB * NPB) * GROUP * sizeof(Real);
     HIPCHK(hipFuncSetAttribute((const void *)basket_greeks_kernel<Real, LR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1886,6 +1938,47 @@ extern "C" int mc_basket_greeks_lr_run_f64(mc_context *c, const mc_basket_f64 *o
                                            mc_result *price, mc_result *delta, mc_result *vega)
 {
     return basket_greeks_run<double, true>(c, o, seed, first, n, price, delta, vega);
+}
+
+// the gamma matrix (basket_gamma_kernel): one pass per BASKET_GAMMA_TILE^2 tile of the upper triangle, n (n + 1) / 2 planes
+// of entries plus the price; both triangles of the caller's n x n array are filled from the upper one
+template <class Real>
+static int basket_gamma_run(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first, uint64_t n,
+                            mc_result *price, mc_result *gamma)
+{
+    if (int rc = check_common(c, o, first, n, price)) return rc;
+    if (!gamma)
+        return fail(MC_ERR_INVALID, "basket gamma: NULL output array");
+    BasketGreeks<Real> k;
+    if (int rc = basket_greeks_setup<Real, true>(c, o, k)) return rc;
+    const int na = o->n, tiles_1d = (na + BASKET_GAMMA_TILE - 1) / BASKET_GAMMA_TILE, tiles = tiles_1d * (tiles_1d + 1) / 2;
+    constexpr int NPB = GenPhilox::npb<Real>();
+    const size_t lds = (size_t)((na + NPB - 1) / NPB * NPB) * GROUP * sizeof(Real);
+    HIPCHK(hipFuncSetAttribute((const void *)basket_gamma_kernel<Real>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    std::vector<mc_result *> out(1 + (size_t)na * (na + 1) / 2);
+    out[0] = price;
+    for (int a = 0, u = 1; a < na; ++a)
+        for (int b = a; b < na; ++b)
+            out[u++] = gamma + (size_t)a * na + b;
+    if (int rc = planes_run(c, sizeof(Real), (int)out.size(), tiles, first, n, n, std::exp(-(double)o->r * (double)o->t), out.data(),
+                            [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
+                                hipLaunchKernelGGL((basket_gamma_kernel<Real>), dim3(g, tiles), dim3(GROUP), lds, st, t, k, make_work(seed, s, 0, 0));
+                            }))
+        return rc;
+    for (int a = 0; a < na; ++a)
+        for (int b = 0; b < a; ++b)
+            gamma[(size_t)a * na + b] = gamma[(size_t)b * na + a];
+    return MC_OK;
+}
+extern "C" int mc_basket_gamma_run_f32(mc_context *c, const mc_basket_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                       mc_result *price, mc_result *gamma)
+{
+    return basket_gamma_run<float>(c, o, seed, first, n, price, gamma);
+}
+extern "C" int mc_basket_gamma_run_f64(mc_context *c, const mc_basket_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                       mc_result *price, mc_result *gamma)
+{
+    return basket_gamma_run<double>(c, o, seed, first, n, price, gamma);
 }
 
 template <class Real, bool LR>

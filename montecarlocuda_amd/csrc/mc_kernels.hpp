@@ -309,6 +309,59 @@ __global__ __launch_bounds__(GROUP) void vanilla_greeks_kernel(const Tail /* fir
     arrive_and_finish(late_tail(acc[0]));
 }
 
+// Second order (the mixed estimator, Glasserman 7.3: the likelihood-ratio derivative of the pathwise first derivative -- no
+// indicator is differentiated twice, and the variance stays far below a pure likelihood-ratio second derivative).  Per path,
+// with dl = I S_T / S the pathwise delta, lr_delta = 1 / (S sigma sqrt T), inv_spot = 1 / S, inv_sigma = 1 / sigma:
+//     gamma = dl (z lr_delta - inv_spot)                    = I S_T / S^2 (z / (sigma sqrt T) - 1)
+//     vanna = dl (z (z inv_sigma - sqrt T) - inv_sigma)     = I S_T / S ((z^2 - 1) / sigma - z sqrt T)
+// Five planes: price, delta, vega (the pathwise kernel's expressions: the same bits), gamma, vanna.
+template <class Opt, class Real>
+__global__ __launch_bounds__(GROUP) void vanilla_greeks2_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const Opt o, const Work w,
+                                                                Real inv_spot)
+{
+    stage_tables<Real>();
+    constexpr int NPB = GenPhilox::npb<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    GenPhilox gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        Real z[NPB];
+        gen.normals(w, w.unit_lo + i, 0u, 1u /*MC_DOMAIN_VANILLA*/, z);
+        const uint64_t unit = ((uint64_t)w.unit_hi << 32) | (uint32_t)(w.unit_lo + i);
+#pragma unroll
+        for (int j = 0; j < NPB; ++j) {
+            const uint64_t path = unit * NPB + j;
+            if (path >= w.first_path && path < w.end_path) {
+                // price, delta and vega are vanilla_greeks_kernel's bits.  There vega's (sqrt_t z - sigma_t) contracts to one fma,
+                // and in fp32 S_T is rounded before every use (in fp64 the payoff is fma(S, e, -K)).  Here the extra uses of S_T and
+                // z let the compiler fuse differently in fp32, so vega's fma is spelled out and the fp32 S_T is made opaque.
+                Real st = greeks_spot(o, z[j]);
+                if constexpr (sizeof(Real) == 4)
+                    asm volatile("" : "+v"(st));
+                const bool itm = st > o.strike;
+                const Real payoff = itm ? st - o.strike : (Real)0;
+                const double pay = (double)payoff;
+                const Real d_r = st / o.spot;
+                const double dl = itm ? (double)d_r : 0.0;
+                const double vg = itm ? (double)(st * fma_r(o.sqrt_t, z[j], -o.sigma_t)) : 0.0;
+                const double gm = itm ? (double)(d_r * fma_r(z[j], o.lr_delta, -inv_spot)) : 0.0;
+                const double va = itm ? (double)(d_r * fma_r(z[j], fma_r(z[j], o.inv_sigma, -o.sqrt_t), -o.inv_sigma)) : 0.0;
+                acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
+                acc[2] += dl, acc[3] = __builtin_fma(dl, dl, acc[3]);
+                acc[4] += vg, acc[5] = __builtin_fma(vg, vg, acc[5]);
+                acc[6] += gm, acc[7] = __builtin_fma(gm, gm, acc[7]);
+                acc[8] += va, acc[9] = __builtin_fma(va, va, acc[9]);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        group_sum2(acc[2 * q], acc[2 * q + 1]);
+        publish_pair(late_tail(acc[2 * q]), q, acc[2 * q], acc[2 * q + 1]);
+    }
+    arrive_and_finish(late_tail(acc[0]));
+}
+
 // =========================================================================================
 // Basket call.  Reference device formulas, dp/MonteCarloKernel.cu:74-101:
 //     bt = L g + d;  s_a = S_a exp((r - v_a^2/2) T + v_a sqrt(T) bt_a);
@@ -1830,6 +1883,126 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
         if (a0 + k < n) {
             publish_pair(t, 1 + a0 + k, acc[2 + 4 * k], acc[3 + 4 * k]);
             publish_pair(t, 1 + n + a0 + k, acc[4 + 4 * k], acc[5 + 4 * k]);
+        }
+    arrive_and_finish(t);
+}
+
+// =========================================================================================
+// Gamma matrix of the basket call by the mixed estimator (the likelihood-ratio derivative of the pathwise delta): with
+// p_a = I w_a S_a(T) / S_a (the pathwise delta term), y = L^-T g and c_b = 1 / (S_b v_b sqrt T) (inv_svt, the LR delta score),
+//     G_ab = 1/2 (p_a y_b c_b + p_b y_a c_a) - [a == b] p_a / S_a
+// (one asset: the vanilla kernel's gamma).  The n (n + 1) / 2 entries a <= b are cut into BASKET_GAMMA_TILE^2 tiles of the upper
+// triangle; the grid's y index is the tile and each workgroup simulates the paths once for its tile (rows ti T.., columns
+// tj T..), keeping one (sum, sum2) pair per entry in registers: 2 T^2 = 32 doubles at T = 4, the budget of basket_greeks_kernel's
+// 8-asset chunk.  Planes: 0 = price (published by tile 0 only, the same bits as basket_greeks_kernel's), 1 + u(a, b) the
+// upper-triangle entry in row-major order, u(a, b) = a n - a (a - 1) / 2 + b - a.  Constant table: basket_greeks_kernel's LR one.
+// =========================================================================================
+constexpr int BASKET_GAMMA_TILE = 4;
+
+template <class Real>
+__global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const BasketGreeks<Real> o, const Work w)
+{
+    constexpr int T = BASKET_GAMMA_TILE;
+    stage_tables<Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Real *g = reinterpret_cast<Real *>(lds_raw) + threadIdx.x;  // this lane's column, stride GROUP
+    constexpr int NPB = GenPhilox::npb<Real>();
+    const int n = o.n, nblk = (n + NPB - 1) / NPB, nt = (n + T - 1) / T;
+    int ti = 0, rem = (int)blockIdx.y;   // tile -> (row tile ti, column tile tj >= ti), workgroup-uniform
+    while (rem >= nt - ti)
+        rem -= nt - ti, ++ti;
+    const int tj = ti + rem, a0 = ti * T, b0 = tj * T;
+    GenPhilox gen(w);
+    typedef const __attribute__((address_space(4))) Real *cptr;
+    const cptr L = (cptr)o.consts, d = L + n * n, mu = d + n, v = mu + n, wt = v + n, s0 = wt + n, inv_s = s0 + n, vt = inv_s + n;
+    const cptr M = vt + n, inv_svt = M + n * n;
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc[2 + 2 * T * T];
+#pragma unroll
+    for (int q = 0; q < 2 + 2 * T * T; ++q)
+        acc[q] = 0;
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        for (int b = 0; b < nblk; ++b) {
+            Real z[NPB];
+            gen.normals(w, w.unit_lo + i, (uint32_t)b, 2u /*MC_DOMAIN_BASKET*/, z);
+#pragma unroll
+            for (int j = 0; j < NPB; ++j)
+                g[(b * NPB + j) * GROUP] = z[j];
+        }
+        Real basket = 0, tr[T], tc[T];
+#pragma unroll
+        for (int k = 0; k < T; ++k)
+            tr[k] = tc[k] = 0;
+        for (int c = 0; c * T < n; ++c) {
+#pragma unroll
+            for (int k = 0; k < T; ++k) {
+                const int a = c * T + k;
+                if (a < n) {   // workgroup-uniform
+                    Real bt = 0;
+                    for (int b = 0; b <= a; ++b)
+                        bt = fma_r(L[a * n + b], g[b * GROUP], bt);
+                    bt += d[a];
+                    const Real t_a = s0[a] * exp_nat(fma_r(v[a] * bt, o.sqrt_t, mu[a])) * wt[a];
+                    basket += t_a;
+                    if (c == ti)   // workgroup-uniform: the tile's row and column assets
+                        tr[k] = t_a;
+                    if (c == tj)
+                        tc[k] = t_a;
+                }
+            }
+        }
+        const bool itm = basket > o.strike;
+        const Real payoff = itm ? basket - o.strike : (Real)0;
+        const double pay = (double)payoff;
+        acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
+        // p and the LR delta score q = y c of the tile's rows (r) and columns (c)
+        Real pr[T], qr[T], pc[T], qc[T];
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            pr[k] = qr[k] = pc[k] = qc[k] = 0;
+            const int a = a0 + k, b = b0 + k;
+            if (a < n) {   // workgroup-uniform
+                Real y = 0;
+                for (int e = a; e < n; ++e)
+                    y = fma_r(M[a * n + e], g[e * GROUP], y);
+                pr[k] = itm ? tr[k] * inv_s[a] : (Real)0;
+                qr[k] = y * inv_svt[a];
+            }
+            if (b < n) {
+                Real y = 0;
+                for (int e = b; e < n; ++e)
+                    y = fma_r(M[b * n + e], g[e * GROUP], y);
+                pc[k] = itm ? tc[k] * inv_s[b] : (Real)0;
+                qc[k] = y * inv_svt[b];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < T; ++r)
+#pragma unroll
+            for (int k = 0; k < T; ++k) {
+                const int a = a0 + r, b = b0 + k;
+                if (a <= b && b < n) {   // workgroup-uniform
+                    Real e = (Real)0.5 * fma_r(pr[r], qc[k], pc[k] * qr[r]);
+                    if (a == b)
+                        e = fma_r(-pr[r], inv_s[a], e);
+                    const double x = (double)e;
+                    acc[2 + 2 * (r * T + k)] += x, acc[3 + 2 * (r * T + k)] = __builtin_fma(x, x, acc[3 + 2 * (r * T + k)]);
+                }
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < 1 + T * T; ++q)
+        group_sum2(acc[2 * q], acc[2 * q + 1]);
+    const tail_ptr t = late_tail(acc[0]);
+    if (blockIdx.y == 0)
+        publish_pair(t, 0, acc[0], acc[1]);
+#pragma unroll
+    for (int r = 0; r < T; ++r)
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            const int a = a0 + r, b = b0 + k;
+            if (a <= b && b < n)
+                publish_pair(t, 1 + a * n - a * (a - 1) / 2 + b - a, acc[2 + 2 * (r * T + k)], acc[3 + 2 * (r * T + k)]);
         }
     arrive_and_finish(t);
 }

@@ -277,6 +277,23 @@ class Engine:
                                                                                         C.byref(price), delta, vega))
         return _estimate(price), [_estimate(x) for x in delta], [_estimate(x) for x in vega]
 
+    def vanilla_greeks2(self, opt, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        """(price, delta, vega, gamma, vanna) Estimates from one pass: delta and vega pathwise (the same bits as vanilla_greeks),
+        gamma and vanna by the mixed estimator (likelihood ratio of the pathwise delta)."""
+        g = _lib.Greeks2()
+        check(getattr(lib(), f"mc_vanilla_greeks2_run_{precision}")(self._ctx, C.byref(_as_option(precision, opt)), seed,
+                                                                     first_path, n_paths, C.byref(g)))
+        return _estimate(g.price), _estimate(g.delta), _estimate(g.vega), _estimate(g.gamma), _estimate(g.vanna)
+
+    def basket_gamma(self, b, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        """(price, gamma) Estimates: gamma[a][b] = d2V / dS_a dS_b, an n x n list of lists (symmetric), by the mixed estimator."""
+        h = _BasketHolder(precision, b)
+        price = _lib.Result()
+        gamma = (_lib.Result * (h.n * h.n))()
+        check(getattr(lib(), f"mc_basket_gamma_run_{precision}")(self._ctx, C.byref(h.struct), seed, first_path, n_paths,
+                                                                  C.byref(price), gamma))
+        return _estimate(price), [[_estimate(gamma[a * h.n + c]) for c in range(h.n)] for a in range(h.n)]
+
     def cva_greeks(self, c, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", lr=False):
         """(cva, delta, vega) Estimates: the CVA and its derivatives with respect to spot and volatility, pathwise or (lr=True)
         by the likelihood ratio."""
