@@ -1060,7 +1060,7 @@ static int vanilla_enqueue(mc_context *c, const typename VanillaTraits<Real>::In
 }
 
 // ---------------------------------------------------------------------------------------
-// vanilla with pathwise Greeks (price, delta, vega)
+// vanilla with Greeks: pathwise, likelihood ratio or second order (vanilla_greeks_kernel)
 // ---------------------------------------------------------------------------------------
 static void greeks_prepare(const mc_option_f32 &o, GreeksF32 &k)
 {
@@ -1172,82 +1172,75 @@ static int greeks_spot_in_range(const In *o)
     return MC_OK;
 }
 
-template <class Real, class In, class Opt, bool LR>
-static int greeks_run(mc_context *c, const In *o, uint64_t seed, uint64_t first, uint64_t n, mc_vanilla_greeks *out)
+// the Greeks kernels implement the plain estimator only
+static int greeks_plain_only(bool variance_reduced)
 {
+    if (variance_reduced)
+        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
+    return MC_OK;
+}
+
+// vanilla_greeks_kernel in form F: price, delta, vega into an mc_vanilla_greeks; SECOND_ORDER also gamma and vanna, into an
+// mc_vanilla_greeks2.  The likelihood-ratio and second-order scores divide by sigma sqrt t
+template <class Real, GreeksForm F, class In, class Out>
+static int vanilla_greeks_run(mc_context *c, const In *o, uint64_t seed, uint64_t first, uint64_t n, Out *out)
+{
+    using Opt = std::conditional_t<sizeof(Real) == 4, GreeksF32, GreeksF64>;
     if (int rc = check_common(c, o, first, n, out)) return rc;
     if (!finite_pos(o->s) || !std::isfinite((double)o->k) || !(o->v >= 0) || !(o->t >= 0) || !std::isfinite((double)o->r))
         return fail(MC_ERR_INVALID, "vanilla: need s>0, finite k, v>=0, t>=0, finite r");
-    if (LR && !((double)o->v > 0 && (double)o->t > 0))
-        return fail(MC_ERR_INVALID, "likelihood-ratio greeks: need v>0 and t>0 (the scores divide by sigma sqrt t)");
-    if (c->antithetic)
-        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
-    if (int rc = greeks_spot_in_range<Real>(o)) return rc;
-    constexpr uint64_t NPB = GenPhilox::npb<Real>();
-    Opt k;
-    greeks_prepare(*o, k);
-    const uint64_t end = first + n, u0 = first / NPB, u1 = (end + NPB - 1) / NPB;
-    mc_result *r[3] = {&out->price, &out->delta, &out->vega};
-    return planes_run(c, sizeof(Real), 3, 1, u0, u1 - u0, n, std::exp(-(double)o->r * (double)o->t), r,
-                      [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
-                          vanilla_greeks_kernel<Opt, Real, LR><<<g, GROUP, 0, st>>>(t, k, make_work(seed, s, first, end));
-                      });
-}
-
-extern "C" int mc_vanilla_greeks_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
-                                         mc_vanilla_greeks *out)
-{
-    return greeks_run<float, mc_option_f32, GreeksF32, false>(c, o, seed, first, n, out);
-}
-extern "C" int mc_vanilla_greeks_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
-                                         mc_vanilla_greeks *out)
-{
-    return greeks_run<double, mc_option_f64, GreeksF64, false>(c, o, seed, first, n, out);
-}
-extern "C" int mc_vanilla_greeks_lr_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
-                                            mc_vanilla_greeks *out)
-{
-    return greeks_run<float, mc_option_f32, GreeksF32, true>(c, o, seed, first, n, out);
-}
-extern "C" int mc_vanilla_greeks_lr_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
-                                            mc_vanilla_greeks *out)
-{
-    return greeks_run<double, mc_option_f64, GreeksF64, true>(c, o, seed, first, n, out);
-}
-
-// second order (vanilla_greeks2_kernel): price, delta, vega, gamma, vanna.  The inputs' checks are the likelihood-ratio
-// Greeks' (the gamma and vanna scores divide by sigma sqrt t)
-template <class Real, class In, class Opt>
-static int greeks2_run(mc_context *c, const In *o, uint64_t seed, uint64_t first, uint64_t n, mc_vanilla_greeks2 *out)
-{
-    if (int rc = check_common(c, o, first, n, out)) return rc;
-    if (!finite_pos(o->s) || !std::isfinite((double)o->k) || !(o->v >= 0) || !(o->t >= 0) || !std::isfinite((double)o->r))
-        return fail(MC_ERR_INVALID, "vanilla: need s>0, finite k, v>=0, t>=0, finite r");
-    if (!((double)o->v > 0 && (double)o->t > 0))
-        return fail(MC_ERR_INVALID, "second-order greeks: need v>0 and t>0 (the scores divide by sigma sqrt t)");
-    if (c->antithetic)
-        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
+    if (F != PATHWISE && !((double)o->v > 0 && (double)o->t > 0))
+        return fail(MC_ERR_INVALID, "%s greeks: need v>0 and t>0 (the scores divide by sigma sqrt t)",
+                    F == SECOND_ORDER ? "second-order" : "likelihood-ratio");
+    if (int rc = greeks_plain_only(c->antithetic)) return rc;
     if (int rc = greeks_spot_in_range<Real>(o)) return rc;
     constexpr uint64_t NPB = GenPhilox::npb<Real>();
     Opt k;
     greeks_prepare(*o, k);
     const Real inv_spot = (Real)(1.0 / (double)o->s);
     const uint64_t end = first + n, u0 = first / NPB, u1 = (end + NPB - 1) / NPB;
-    mc_result *r[5] = {&out->price, &out->delta, &out->vega, &out->gamma, &out->vanna};
-    return planes_run(c, sizeof(Real), 5, 1, u0, u1 - u0, n, std::exp(-(double)o->r * (double)o->t), r,
+    mc_result *r[5] = {&out->price, &out->delta, &out->vega};
+    if constexpr (F == SECOND_ORDER)
+        r[3] = &out->gamma, r[4] = &out->vanna;
+    return planes_run(c, sizeof(Real), greeks_planes(F), 1, u0, u1 - u0, n, std::exp(-(double)o->r * (double)o->t), r,
                       [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
-                          vanilla_greeks2_kernel<Opt, Real><<<g, GROUP, 0, st>>>(t, k, make_work(seed, s, first, end), inv_spot);
+                          const Work w = make_work(seed, s, first, end);
+                          if constexpr (F == SECOND_ORDER)
+                              vanilla_greeks_kernel<Opt, Real, F><<<g, GROUP, 0, st>>>(t, k, w, inv_spot);
+                          else
+                              vanilla_greeks_kernel<Opt, Real, F><<<g, GROUP, 0, st>>>(t, k, w);
                       });
+}
+
+extern "C" int mc_vanilla_greeks_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                         mc_vanilla_greeks *out)
+{
+    return vanilla_greeks_run<float, PATHWISE>(c, o, seed, first, n, out);
+}
+extern "C" int mc_vanilla_greeks_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                         mc_vanilla_greeks *out)
+{
+    return vanilla_greeks_run<double, PATHWISE>(c, o, seed, first, n, out);
+}
+extern "C" int mc_vanilla_greeks_lr_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                            mc_vanilla_greeks *out)
+{
+    return vanilla_greeks_run<float, LIKELIHOOD_RATIO>(c, o, seed, first, n, out);
+}
+extern "C" int mc_vanilla_greeks_lr_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
+                                            mc_vanilla_greeks *out)
+{
+    return vanilla_greeks_run<double, LIKELIHOOD_RATIO>(c, o, seed, first, n, out);
 }
 extern "C" int mc_vanilla_greeks2_run_f32(mc_context *c, const mc_option_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
                                           mc_vanilla_greeks2 *out)
 {
-    return greeks2_run<float, mc_option_f32, GreeksF32>(c, o, seed, first, n, out);
+    return vanilla_greeks_run<float, SECOND_ORDER>(c, o, seed, first, n, out);
 }
 extern "C" int mc_vanilla_greeks2_run_f64(mc_context *c, const mc_option_f64 *o, uint64_t seed, uint64_t first, uint64_t n,
                                           mc_vanilla_greeks2 *out)
 {
-    return greeks2_run<double, mc_option_f64, GreeksF64>(c, o, seed, first, n, out);
+    return vanilla_greeks_run<double, SECOND_ORDER>(c, o, seed, first, n, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1828,8 +1821,7 @@ static int basket_greeks_setup(mc_context *c, const typename BasketIn<Real>::typ
         return fail(MC_ERR_INVALID, "basket: NULL array");
     if (!(o->t >= 0) || !std::isfinite((double)o->r) || !std::isfinite((double)o->k))
         return fail(MC_ERR_INVALID, "basket: need t>=0 and finite r, k");
-    if (c->antithetic || c->control)
-        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
+    if (int rc = greeks_plain_only(c->antithetic || c->control)) return rc;
     const int na = o->n;
     const double sqrt_t = std::sqrt((double)o->t);
     // table: L[n*n] | d | mu | v | w | s | 1/s | v t      (the reference's unfolded constants, dp/MonteCarloKernel.cu:74-101)
@@ -1895,6 +1887,22 @@ static int basket_greeks_setup(mc_context *c, const typename BasketIn<Real>::typ
     return MC_OK;
 }
 
+// a basket Greeks kernel over the call: `passes` workgroups per x position (grid y), the lane's LDS column of the path's normals
+// (whole blocks of NPB), out[q] = plane q
+template <class Real>
+static int basket_planes_run(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first, uint64_t n,
+                             void (*kernel)(Tail, BasketGreeks<Real>, Work), const BasketGreeks<Real> &k, int passes,
+                             std::vector<mc_result *> &out)
+{
+    constexpr int NPB = GenPhilox::npb<Real>();
+    const size_t lds = (size_t)((o->n + NPB - 1) / NPB * NPB) * GROUP * sizeof(Real);
+    HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return planes_run(c, sizeof(Real), (int)out.size(), passes, first, n, n, std::exp(-(double)o->r * (double)o->t), out.data(),
+                      [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
+                          hipLaunchKernelGGL(kernel, dim3(g, passes), dim3(GROUP), lds, st, t, k, make_work(seed, s, 0, 0));
+                      });
+}
+
 template <class Real, bool LR>
 static int basket_greeks_run(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first, uint64_t n,
                              mc_result *price, mc_result *delta, mc_result *vega)
@@ -1905,19 +1913,13 @@ static int basket_greeks_run(mc_context *c, const typename BasketIn<Real>::type 
     BasketGreeks<Real> k;
     if (int rc = basket_greeks_setup<Real, LR>(c, o, k)) return rc;
     const int na = o->n;
-    constexpr int NPB = GenPhilox::npb<Real>();
-    const size_t lds = (size_t)((na + NPB - 1) / NPB * NPB) * GROUP * sizeof(Real);
-    HIPCHK(hipFuncSetAttribute((const void *)basket_greeks_kernel<Real, LR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     std::vector<mc_result *> out(1 + 2 * (size_t)na);
     out[0] = price;
     for (int a = 0; a < na; ++a)
         out[1 + a] = delta + a, out[1 + na + a] = vega + a;
     // one pass per BASKET_GREEKS_CHUNK assets: the grid's y index is the chunk
     const int chunks = (na + BASKET_GREEKS_CHUNK - 1) / BASKET_GREEKS_CHUNK;
-    return planes_run(c, sizeof(Real), 1 + 2 * na, chunks, first, n, n, std::exp(-(double)o->r * (double)o->t), out.data(),
-                      [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
-                          hipLaunchKernelGGL((basket_greeks_kernel<Real, LR>), dim3(g, chunks), dim3(GROUP), lds, st, t, k, make_work(seed, s, 0, 0));
-                      });
+    return basket_planes_run<Real>(c, o, seed, first, n, basket_greeks_kernel<Real, LR>, k, chunks, out);
 }
 extern "C" int mc_basket_greeks_run_f32(mc_context *c, const mc_basket_f32 *o, uint64_t seed, uint64_t first, uint64_t n,
                                         mc_result *price, mc_result *delta, mc_result *vega)
@@ -1952,19 +1954,12 @@ static int basket_gamma_run(mc_context *c, const typename BasketIn<Real>::type *
     BasketGreeks<Real> k;
     if (int rc = basket_greeks_setup<Real, true>(c, o, k)) return rc;
     const int na = o->n, tiles_1d = (na + BASKET_GAMMA_TILE - 1) / BASKET_GAMMA_TILE, tiles = tiles_1d * (tiles_1d + 1) / 2;
-    constexpr int NPB = GenPhilox::npb<Real>();
-    const size_t lds = (size_t)((na + NPB - 1) / NPB * NPB) * GROUP * sizeof(Real);
-    HIPCHK(hipFuncSetAttribute((const void *)basket_gamma_kernel<Real>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     std::vector<mc_result *> out(1 + (size_t)na * (na + 1) / 2);
     out[0] = price;
     for (int a = 0, u = 1; a < na; ++a)
         for (int b = a; b < na; ++b)
             out[u++] = gamma + (size_t)a * na + b;
-    if (int rc = planes_run(c, sizeof(Real), (int)out.size(), tiles, first, n, n, std::exp(-(double)o->r * (double)o->t), out.data(),
-                            [&](const Tail &t, const Segment &s, int g, hipStream_t st) {
-                                hipLaunchKernelGGL((basket_gamma_kernel<Real>), dim3(g, tiles), dim3(GROUP), lds, st, t, k, make_work(seed, s, 0, 0));
-                            }))
-        return rc;
+    if (int rc = basket_planes_run<Real>(c, o, seed, first, n, basket_gamma_kernel<Real>, k, tiles, out)) return rc;
     for (int a = 0; a < na; ++a)
         for (int b = 0; b < a; ++b)
             gamma[(size_t)a * na + b] = gamma[(size_t)b * na + a];
@@ -1985,8 +1980,7 @@ template <class Real, bool LR>
 static int cva_greeks_run(mc_context *c, const typename CvaIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n, mc_cva_greeks *out)
 {
     if (int rc = check_common(c, v, first, n, out)) return rc;
-    if (c->antithetic)
-        return fail(MC_ERR_UNSUPPORTED, "greeks: only the plain estimator is implemented");
+    if (int rc = greeks_plain_only(c->antithetic)) return rc;
     if (int rc = begin_call(c, c->stream)) return rc;
     CvaArgs<Real> args;
     if (int rc = cva_table_ready<Real>(c, v, c->stream, args)) return rc;

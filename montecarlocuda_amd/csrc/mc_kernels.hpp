@@ -252,28 +252,39 @@ __global__ __launch_bounds__(GROUP) void vanilla_masked_kernel(const Tail /* fir
 }
 
 // =========================================================================================
-// Vanilla call with pathwise Greeks (the reference prices only).  Per path, on the same
-// normal as the pricing kernels:  S_T = S exp(drift + vol z),  I = [S_T > K],
-//     payoff = I (S_T - K),   d payoff / dS = I S_T / S,   d payoff / d sigma = I S_T (sqrt(T) z - sigma T)
-// Three (sum, sum2) pairs per workgroup, one per plane of the call's pair buffer: q = price, delta, vega.
-// Always honours the path window (no separate hot variant: a secondary kernel).
-// =========================================================================================
-// lr_delta = 1 / (S sigma sqrt T), inv_sigma = 1 / sigma: the scores of the likelihood-ratio estimators (LR = true):
+// Vanilla call with its Greeks (the reference prices only).  Per path, on the same normal as the pricing kernels:
+//     S_T = S exp(drift + vol z),   I = [S_T > K],   payoff = I (S_T - K)
+// in one of three forms (GreeksForm):
+// PATHWISE:          d payoff / dS = I S_T / S,   d payoff / d sigma = I S_T (sqrt(T) z - sigma T)
+// LIKELIHOOD_RATIO:  differentiate the lognormal density instead of the payoff (no indicator, so they also serve payoffs with
+//                    jumps); with lr_delta = 1 / (S sigma sqrt T), inv_sigma = 1 / sigma:
 //     delta = payoff z / (S sigma sqrt T),   vega = payoff ((z^2 - 1) / sigma - z sqrt T)
-// (differentiate the lognormal density instead of the payoff: no indicator, so they also serve payoffs with jumps).
+// SECOND_ORDER:      the pathwise delta and vega, and gamma and vanna by the mixed estimator (Glasserman 7.3: the likelihood-ratio
+//                    derivative of the pathwise first derivative -- no indicator is differentiated twice, and the variance stays far
+//                    below a pure likelihood-ratio second derivative); with dl = I S_T / S the pathwise delta, inv_spot = 1 / S:
+//     gamma = dl (z lr_delta - inv_spot)                    = I S_T / S^2 (z / (sigma sqrt T) - 1)
+//     vanna = dl (z (z inv_sigma - sqrt T) - inv_sigma)     = I S_T / S ((z^2 - 1) / sigma - z sqrt T)
+// One (sum, sum2) pair per workgroup and plane of the call's pair buffer: price, delta, vega (, gamma, vanna).  Always honours
+// the path window (no separate hot variant: a secondary kernel).
+// =========================================================================================
 struct GreeksF32 { float drift2, vol2, spot, strike, sqrt_t, sigma_t, lr_delta, inv_sigma; };   // exponent in log2 units
 struct GreeksF64 { double drift, vol, spot, strike, sqrt_t, sigma_t, lr_delta, inv_sigma; };
+enum GreeksForm { PATHWISE, LIKELIHOOD_RATIO, SECOND_ORDER };
+constexpr int greeks_planes(GreeksForm f) { return f == SECOND_ORDER ? 5 : 3; }
 
 __device__ __forceinline__ float greeks_spot(const GreeksF32 &o, float z) { return o.spot * __builtin_amdgcn_exp2f(__builtin_fmaf(o.vol2, z, o.drift2)); }
 __device__ __forceinline__ double greeks_spot(const GreeksF64 &o, double z) { return o.spot * exp_f64(__builtin_fma(o.vol, z, o.drift)); }
 
-template <class Opt, class Real, bool LR>
-__global__ __launch_bounds__(GROUP) void vanilla_greeks_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const Opt o, const Work w)
+// inv_spot = 1 / S: an argument of the SECOND_ORDER form only (the pack is empty in the first-order forms, whose kernel arguments
+// stay (Tail, Opt, Work))
+template <class Opt, class Real, GreeksForm F, class... InvSpot>
+__global__ __launch_bounds__(GROUP) void vanilla_greeks_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const Opt o, const Work w,
+                                                               const InvSpot... inv_spot)
 {
     stage_tables<Real>();
     constexpr int NPB = GenPhilox::npb<Real>();
     const uint32_t stride = gridDim.x * GROUP;
-    double acc[6] = {0, 0, 0, 0, 0, 0};
+    double acc[2 * greeks_planes(F)] = {};
     GenPhilox gen(w);
     for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
         Real z[NPB];
@@ -283,81 +294,43 @@ __global__ __launch_bounds__(GROUP) void vanilla_greeks_kernel(const Tail /* fir
         for (int j = 0; j < NPB; ++j) {
             const uint64_t path = unit * NPB + j;
             if (path >= w.first_path && path < w.end_path) {
-                const Real st = greeks_spot(o, z[j]);
-                const bool itm = st > o.strike;
-                const Real payoff = itm ? st - o.strike : (Real)0;
-                const double pay = (double)payoff;
-                double dl, vg;
-                if (LR) {
-                    dl = (double)(payoff * z[j] * o.lr_delta);
-                    vg = (double)(payoff * ((z[j] * z[j] - (Real)1) * o.inv_sigma - z[j] * o.sqrt_t));
-                } else {
-                    dl = itm ? (double)(st / o.spot) : 0.0;
-                    vg = itm ? (double)(st * (o.sqrt_t * z[j] - o.sigma_t)) : 0.0;
-                }
-                acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
-                acc[2] += dl, acc[3] = __builtin_fma(dl, dl, acc[3]);
-                acc[4] += vg, acc[5] = __builtin_fma(vg, vg, acc[5]);
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        group_sum2(acc[2 * q], acc[2 * q + 1]);
-        publish_pair(late_tail(acc[2 * q]), q, acc[2 * q], acc[2 * q + 1]);
-    }
-    arrive_and_finish(late_tail(acc[0]));
-}
-
-// Second order (the mixed estimator, Glasserman 7.3: the likelihood-ratio derivative of the pathwise first derivative -- no
-// indicator is differentiated twice, and the variance stays far below a pure likelihood-ratio second derivative).  Per path,
-// with dl = I S_T / S the pathwise delta, lr_delta = 1 / (S sigma sqrt T), inv_spot = 1 / S, inv_sigma = 1 / sigma:
-//     gamma = dl (z lr_delta - inv_spot)                    = I S_T / S^2 (z / (sigma sqrt T) - 1)
-//     vanna = dl (z (z inv_sigma - sqrt T) - inv_sigma)     = I S_T / S ((z^2 - 1) / sigma - z sqrt T)
-// Five planes: price, delta, vega (the pathwise kernel's expressions: the same bits), gamma, vanna.
-template <class Opt, class Real>
-__global__ __launch_bounds__(GROUP) void vanilla_greeks2_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const Opt o, const Work w,
-                                                                Real inv_spot)
-{
-    stage_tables<Real>();
-    constexpr int NPB = GenPhilox::npb<Real>();
-    const uint32_t stride = gridDim.x * GROUP;
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    GenPhilox gen(w);
-    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
-        Real z[NPB];
-        gen.normals(w, w.unit_lo + i, 0u, 1u /*MC_DOMAIN_VANILLA*/, z);
-        const uint64_t unit = ((uint64_t)w.unit_hi << 32) | (uint32_t)(w.unit_lo + i);
-#pragma unroll
-        for (int j = 0; j < NPB; ++j) {
-            const uint64_t path = unit * NPB + j;
-            if (path >= w.first_path && path < w.end_path) {
-                // price, delta and vega are vanilla_greeks_kernel's bits.  There vega's (sqrt_t z - sigma_t) contracts to one fma,
-                // and in fp32 S_T is rounded before every use (in fp64 the payoff is fma(S, e, -K)).  Here the extra uses of S_T and
-                // z let the compiler fuse differently in fp32, so vega's fma is spelled out and the fp32 S_T is made opaque.
                 Real st = greeks_spot(o, z[j]);
-                if constexpr (sizeof(Real) == 4)
+                // In the first-order forms, fp32 S_T is rounded before every use (in fp64 the payoff is fma(S, e, -K)).  The second
+                // order's extra uses of S_T and z let the compiler fuse differently in fp32, so there S_T is made opaque: price, delta
+                // and vega stay the pathwise form's bits.
+                if constexpr (F == SECOND_ORDER && sizeof(Real) == 4)
                     asm volatile("" : "+v"(st));
                 const bool itm = st > o.strike;
                 const Real payoff = itm ? st - o.strike : (Real)0;
                 const double pay = (double)payoff;
-                const Real d_r = st / o.spot;
-                const double dl = itm ? (double)d_r : 0.0;
-                const double vg = itm ? (double)(st * fma_r(o.sqrt_t, z[j], -o.sigma_t)) : 0.0;
-                const double gm = itm ? (double)(d_r * fma_r(z[j], o.lr_delta, -inv_spot)) : 0.0;
-                const double va = itm ? (double)(d_r * fma_r(z[j], fma_r(z[j], o.inv_sigma, -o.sqrt_t), -o.inv_sigma)) : 0.0;
-                acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
-                acc[2] += dl, acc[3] = __builtin_fma(dl, dl, acc[3]);
-                acc[4] += vg, acc[5] = __builtin_fma(vg, vg, acc[5]);
-                acc[6] += gm, acc[7] = __builtin_fma(gm, gm, acc[7]);
-                acc[8] += va, acc[9] = __builtin_fma(va, va, acc[9]);
+                double dl, vg, gm, va;   // gm, va: SECOND_ORDER only
+                if constexpr (F == LIKELIHOOD_RATIO) {
+                    dl = (double)(payoff * z[j] * o.lr_delta);
+                    vg = (double)(payoff * ((z[j] * z[j] - (Real)1) * o.inv_sigma - z[j] * o.sqrt_t));
+                } else if constexpr (F == PATHWISE) {
+                    dl = itm ? (double)(st / o.spot) : 0.0;
+                    vg = itm ? (double)(st * (o.sqrt_t * z[j] - o.sigma_t)) : 0.0;
+                } else {   // the pathwise delta and vega; vega's fma spelled out (the pathwise form's (sqrt_t z - sigma_t) contracts to it)
+                    const Real d_r = st / o.spot;
+                    dl = itm ? (double)d_r : 0.0;
+                    vg = itm ? (double)(st * fma_r(o.sqrt_t, z[j], -o.sigma_t)) : 0.0;
+                    gm = itm ? (double)(d_r * fma_r(z[j], o.lr_delta, -inv_spot...)) : 0.0;
+                    va = itm ? (double)(d_r * fma_r(z[j], fma_r(z[j], o.inv_sigma, -o.sqrt_t), -o.inv_sigma)) : 0.0;
+                }
+                pair_add(acc, 0, pay);
+                pair_add(acc, 1, dl);
+                pair_add(acc, 2, vg);
+                if constexpr (F == SECOND_ORDER) {
+                    pair_add(acc, 3, gm);
+                    pair_add(acc, 4, va);
+                }
             }
         }
     }
 #pragma unroll
-    for (int q = 0; q < 5; ++q) {
+    for (int q = 0; q < greeks_planes(F); ++q) {
         group_sum2(acc[2 * q], acc[2 * q + 1]);
-        publish_pair(late_tail(acc[2 * q]), q, acc[2 * q], acc[2 * q + 1]);
+        pair_publish(late_tail(acc[2 * q]), acc, q, q);
     }
     arrive_and_finish(late_tail(acc[0]));
 }
@@ -1799,6 +1772,30 @@ constexpr int BASKET_GREEKS_CHUNK = MC_BASKET_GREEKS_CHUNK;
 __device__ __forceinline__ float exp_nat(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ double exp_nat(double x) { return exp_f64(x); }
 
+// What basket_greeks_kernel and basket_gamma_kernel share: the constant table's arrays (scalar loads; M .. mcoef in the LR table
+// only) and the staging of a path's normals into the lane's LDS column.  The loops over the assets stay in the kernels: moved into
+// a helper, a loop whose trip count is only known at run time is optimised before it is inlined and compiles to different code.
+template <class Real>
+struct BasketTable {
+    typedef const __attribute__((address_space(4))) Real *cptr;
+    static constexpr int NPB = GenPhilox::npb<Real>();
+    int n, nblk;   // assets, blocks of NPB normals per path
+    cptr L, d, mu, v, wt, s0, inv_s, vt, M, inv_svt, inv_v, mcoef;
+    __device__ __forceinline__ BasketTable(const BasketGreeks<Real> &o)
+        : n(o.n), nblk((o.n + NPB - 1) / NPB), L((cptr)o.consts), d(L + n * n), mu(d + n), v(mu + n), wt(v + n), s0(wt + n),
+          inv_s(s0 + n), vt(inv_s + n), M(vt + n), inv_svt(M + n * n), inv_v(inv_svt + n), mcoef(inv_v + n) {}
+
+    // block b of the unit's normals into the lane's column g (stride GROUP): assets b NPB ..
+    __device__ __forceinline__ void stage(GenPhilox &gen, const Work &w, uint32_t unit, int b, Real *g) const
+    {
+        Real z[NPB];
+        gen.normals(w, unit, (uint32_t)b, 2u /*MC_DOMAIN_BASKET*/, z);
+#pragma unroll
+        for (int j = 0; j < NPB; ++j)
+            g[(b * NPB + j) * GROUP] = z[j];
+    }
+};
+
 template <class Real, bool LR>
 __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const BasketGreeks<Real> o, const Work w)
 {
@@ -1806,25 +1803,17 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
     stage_tables<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     Real *g = reinterpret_cast<Real *>(lds_raw) + threadIdx.x;  // this lane's column, stride GROUP
-    constexpr int NPB = GenPhilox::npb<Real>();
-    const int n = o.n, nblk = (n + NPB - 1) / NPB, chunk = blockIdx.y, a0 = chunk * A;
+    const BasketTable<Real> tb(o);
+    const int n = tb.n, chunk = blockIdx.y, a0 = chunk * A;
     GenPhilox gen(w);
-    typedef const __attribute__((address_space(4))) Real *cptr;
-    const cptr L = (cptr)o.consts, d = L + n * n, mu = d + n, v = mu + n, wt = v + n, s0 = wt + n, inv_s = s0 + n, vt = inv_s + n;
-    const cptr M = vt + n, inv_svt = M + n * n, inv_v = inv_svt + n, mcoef = inv_v + n;   // LR only
     const uint32_t stride = gridDim.x * GROUP;
-    double acc[2 + 4 * A];
+    double acc[2 + 4 * A];   // pairs: price, then delta and vega of the chunk's asset a0 + k (1 + 2 k, 2 + 2 k)
 #pragma unroll
     for (int q = 0; q < 2 + 4 * A; ++q)
         acc[q] = 0;
     for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
-        for (int b = 0; b < nblk; ++b) {
-            Real z[NPB];
-            gen.normals(w, w.unit_lo + i, (uint32_t)b, 2u /*MC_DOMAIN_BASKET*/, z);
-#pragma unroll
-            for (int j = 0; j < NPB; ++j)
-                g[(b * NPB + j) * GROUP] = z[j];
-        }
+        for (int b = 0; b < tb.nblk; ++b)
+            tb.stage(gen, w, w.unit_lo + i, b, g);
         Real basket = 0, term[A], bts[A];
 #pragma unroll
         for (int k = 0; k < A; ++k)
@@ -1836,10 +1825,10 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
                 if (a < n) {   // workgroup-uniform
                     Real bt = 0;
                     for (int b = 0; b <= a; ++b)
-                        bt = fma_r(L[a * n + b], g[b * GROUP], bt);
+                        bt = fma_r(tb.L[a * n + b], g[b * GROUP], bt);
                     const Real bt0 = bt;   // (L g)_a, before the drift
-                    bt += d[a];
-                    const Real t_a = s0[a] * exp_nat(fma_r(v[a] * bt, o.sqrt_t, mu[a])) * wt[a];
+                    bt += tb.d[a];
+                    const Real t_a = tb.s0[a] * exp_nat(fma_r(tb.v[a] * bt, o.sqrt_t, tb.mu[a])) * tb.wt[a];
                     basket += t_a;
                     if (c == chunk) {   // workgroup-uniform: the assets whose derivatives this workgroup accumulates
                         term[k] = t_a;
@@ -1850,8 +1839,7 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
         }
         const bool itm = basket > o.strike;
         const Real payoff = itm ? basket - o.strike : (Real)0;
-        const double pay = (double)payoff;
-        acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
+        pair_add(acc, 0, (double)payoff);
 #pragma unroll
         for (int k = 0; k < A; ++k) {
             const int a = a0 + k;
@@ -1860,15 +1848,15 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
                 if constexpr (LR) {
                     Real y = 0;
                     for (int b = a; b < n; ++b)
-                        y = fma_r(M[a * n + b], g[b * GROUP], y);
-                    dl = (double)(payoff * (y * inv_svt[a]));
-                    vg = (double)(payoff * fma_r(fma_r(y, bts[k], (Real)-1), inv_v[a], mcoef[a] * y));
+                        y = fma_r(tb.M[a * n + b], g[b * GROUP], y);
+                    dl = (double)(payoff * (y * tb.inv_svt[a]));
+                    vg = (double)(payoff * fma_r(fma_r(y, bts[k], (Real)-1), tb.inv_v[a], tb.mcoef[a] * y));
                 } else {
-                    dl = itm ? (double)(term[k] * inv_s[a]) : 0.0;
-                    vg = itm ? (double)(term[k] * (bts[k] * o.sqrt_t - vt[a])) : 0.0;
+                    dl = itm ? (double)(term[k] * tb.inv_s[a]) : 0.0;
+                    vg = itm ? (double)(term[k] * (bts[k] * o.sqrt_t - tb.vt[a])) : 0.0;
                 }
-                acc[2 + 4 * k] += dl, acc[3 + 4 * k] = __builtin_fma(dl, dl, acc[3 + 4 * k]);
-                acc[4 + 4 * k] += vg, acc[5 + 4 * k] = __builtin_fma(vg, vg, acc[5 + 4 * k]);
+                pair_add(acc, 1 + 2 * k, dl);
+                pair_add(acc, 2 + 2 * k, vg);
             }
         }
     }
@@ -1877,12 +1865,12 @@ __global__ __launch_bounds__(GROUP) void basket_greeks_kernel(const Tail /* firs
         group_sum2(acc[2 * q], acc[2 * q + 1]);
     const tail_ptr t = late_tail(acc[0]);
     if (chunk == 0)
-        publish_pair(t, 0, acc[0], acc[1]);
+        pair_publish(t, acc, 0, 0);
 #pragma unroll
     for (int k = 0; k < A; ++k)
         if (a0 + k < n) {
-            publish_pair(t, 1 + a0 + k, acc[2 + 4 * k], acc[3 + 4 * k]);
-            publish_pair(t, 1 + n + a0 + k, acc[4 + 4 * k], acc[5 + 4 * k]);
+            pair_publish(t, acc, 1 + 2 * k, 1 + a0 + k);
+            pair_publish(t, acc, 2 + 2 * k, 1 + n + a0 + k);
         }
     arrive_and_finish(t);
 }
@@ -1906,29 +1894,21 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
     stage_tables<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     Real *g = reinterpret_cast<Real *>(lds_raw) + threadIdx.x;  // this lane's column, stride GROUP
-    constexpr int NPB = GenPhilox::npb<Real>();
-    const int n = o.n, nblk = (n + NPB - 1) / NPB, nt = (n + T - 1) / T;
+    const int n = o.n, nt = (n + T - 1) / T;
     int ti = 0, rem = (int)blockIdx.y;   // tile -> (row tile ti, column tile tj >= ti), workgroup-uniform
     while (rem >= nt - ti)
         rem -= nt - ti, ++ti;
     const int tj = ti + rem, a0 = ti * T, b0 = tj * T;
     GenPhilox gen(w);
-    typedef const __attribute__((address_space(4))) Real *cptr;
-    const cptr L = (cptr)o.consts, d = L + n * n, mu = d + n, v = mu + n, wt = v + n, s0 = wt + n, inv_s = s0 + n, vt = inv_s + n;
-    const cptr M = vt + n, inv_svt = M + n * n;
+    const BasketTable<Real> tb(o);
     const uint32_t stride = gridDim.x * GROUP;
-    double acc[2 + 2 * T * T];
+    double acc[2 + 2 * T * T];   // pairs: price, then entry (a0 + r, b0 + k) in 1 + r T + k
 #pragma unroll
     for (int q = 0; q < 2 + 2 * T * T; ++q)
         acc[q] = 0;
     for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
-        for (int b = 0; b < nblk; ++b) {
-            Real z[NPB];
-            gen.normals(w, w.unit_lo + i, (uint32_t)b, 2u /*MC_DOMAIN_BASKET*/, z);
-#pragma unroll
-            for (int j = 0; j < NPB; ++j)
-                g[(b * NPB + j) * GROUP] = z[j];
-        }
+        for (int b = 0; b < tb.nblk; ++b)
+            tb.stage(gen, w, w.unit_lo + i, b, g);
         Real basket = 0, tr[T], tc[T];
 #pragma unroll
         for (int k = 0; k < T; ++k)
@@ -1940,9 +1920,9 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
                 if (a < n) {   // workgroup-uniform
                     Real bt = 0;
                     for (int b = 0; b <= a; ++b)
-                        bt = fma_r(L[a * n + b], g[b * GROUP], bt);
-                    bt += d[a];
-                    const Real t_a = s0[a] * exp_nat(fma_r(v[a] * bt, o.sqrt_t, mu[a])) * wt[a];
+                        bt = fma_r(tb.L[a * n + b], g[b * GROUP], bt);
+                    bt += tb.d[a];
+                    const Real t_a = tb.s0[a] * exp_nat(fma_r(tb.v[a] * bt, o.sqrt_t, tb.mu[a])) * tb.wt[a];
                     basket += t_a;
                     if (c == ti)   // workgroup-uniform: the tile's row and column assets
                         tr[k] = t_a;
@@ -1953,8 +1933,7 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
         }
         const bool itm = basket > o.strike;
         const Real payoff = itm ? basket - o.strike : (Real)0;
-        const double pay = (double)payoff;
-        acc[0] += pay, acc[1] = __builtin_fma(pay, pay, acc[1]);
+        pair_add(acc, 0, (double)payoff);
         // p and the LR delta score q = y c of the tile's rows (r) and columns (c)
         Real pr[T], qr[T], pc[T], qc[T];
 #pragma unroll
@@ -1964,16 +1943,16 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
             if (a < n) {   // workgroup-uniform
                 Real y = 0;
                 for (int e = a; e < n; ++e)
-                    y = fma_r(M[a * n + e], g[e * GROUP], y);
-                pr[k] = itm ? tr[k] * inv_s[a] : (Real)0;
-                qr[k] = y * inv_svt[a];
+                    y = fma_r(tb.M[a * n + e], g[e * GROUP], y);
+                pr[k] = itm ? tr[k] * tb.inv_s[a] : (Real)0;
+                qr[k] = y * tb.inv_svt[a];
             }
             if (b < n) {
                 Real y = 0;
                 for (int e = b; e < n; ++e)
-                    y = fma_r(M[b * n + e], g[e * GROUP], y);
-                pc[k] = itm ? tc[k] * inv_s[b] : (Real)0;
-                qc[k] = y * inv_svt[b];
+                    y = fma_r(tb.M[b * n + e], g[e * GROUP], y);
+                pc[k] = itm ? tc[k] * tb.inv_s[b] : (Real)0;
+                qc[k] = y * tb.inv_svt[b];
             }
         }
 #pragma unroll
@@ -1984,9 +1963,8 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
                 if (a <= b && b < n) {   // workgroup-uniform
                     Real e = (Real)0.5 * fma_r(pr[r], qc[k], pc[k] * qr[r]);
                     if (a == b)
-                        e = fma_r(-pr[r], inv_s[a], e);
-                    const double x = (double)e;
-                    acc[2 + 2 * (r * T + k)] += x, acc[3 + 2 * (r * T + k)] = __builtin_fma(x, x, acc[3 + 2 * (r * T + k)]);
+                        e = fma_r(-pr[r], tb.inv_s[a], e);
+                    pair_add(acc, 1 + r * T + k, (double)e);
                 }
             }
     }
@@ -1995,14 +1973,14 @@ __global__ __launch_bounds__(GROUP) void basket_gamma_kernel(const Tail /* first
         group_sum2(acc[2 * q], acc[2 * q + 1]);
     const tail_ptr t = late_tail(acc[0]);
     if (blockIdx.y == 0)
-        publish_pair(t, 0, acc[0], acc[1]);
+        pair_publish(t, acc, 0, 0);
 #pragma unroll
     for (int r = 0; r < T; ++r)
 #pragma unroll
         for (int k = 0; k < T; ++k) {
             const int a = a0 + r, b = b0 + k;
             if (a <= b && b < n)
-                publish_pair(t, 1 + a * n - a * (a - 1) / 2 + b - a, acc[2 + 2 * (r * T + k)], acc[3 + 2 * (r * T + k)]);
+                pair_publish(t, acc, 1 + r * T + k, 1 + a * n - a * (a - 1) / 2 + b - a);
         }
     arrive_and_finish(t);
 }
@@ -2058,7 +2036,7 @@ __global__ __launch_bounds__(GROUP) void cva_greeks_kernel(const Tail /* first a
     GenPhilox gen(w);
     typedef const __attribute__((address_space(4))) Real *cptr;
     const cptr sqrt_tau = (cptr)o.extra, sig_t = sqrt_tau + n_dates;
-    double acc[6] = {0, 0, 0, 0, 0, 0};
+    double acc[6] = {};
     for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
         Real W = 0, cva = 0, delta = 0, vega = 0, score = 0, z_first = 0, z[NPB];
         for (int j = 0; j < n_dates; ++j) {   // wave-uniform: table rows through scalar loads
@@ -2097,9 +2075,9 @@ __global__ __launch_bounds__(GROUP) void cva_greeks_kernel(const Tail /* first a
         const double c = (double)cva_path;
         const double dl = LR ? (double)(cva_path * (z_first * lr_delta)) : (double)(delta * o.lgd * inv_spot);
         const double vg = LR ? (double)fma_r(cva_path, score, vega * o.lgd) : (double)(vega * o.lgd);
-        acc[0] += c, acc[1] = __builtin_fma(c, c, acc[1]);
-        acc[2] += dl, acc[3] = __builtin_fma(dl, dl, acc[3]);
-        acc[4] += vg, acc[5] = __builtin_fma(vg, vg, acc[5]);
+        pair_add(acc, 0, c);
+        pair_add(acc, 1, dl);
+        pair_add(acc, 2, vg);
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -2107,7 +2085,7 @@ __global__ __launch_bounds__(GROUP) void cva_greeks_kernel(const Tail /* first a
     const tail_ptr t = late_tail(acc[0]);
 #pragma unroll
     for (int q = 0; q < 3; ++q)
-        publish_pair(t, q, acc[2 * q], acc[2 * q + 1]);
+        pair_publish(t, acc, q, q);
     arrive_and_finish(t);
 }
 

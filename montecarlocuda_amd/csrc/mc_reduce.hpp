@@ -202,6 +202,20 @@ __device__ __forceinline__ void arrive_and_finish(tail_ptr t)
         __hip_atomic_store((gu32_t *)t->tickets + threadIdx.x * TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The Greeks kernels' sums: pair q of a lane's `double acc[2 P] = {}` is (acc[2 q], acc[2 q + 1]), one pair per plane of the
+// call's pair buffer.  Per pair only, the loops over the pairs stay in the kernels: inlined from a helper, a loop of group_sum2
+// calls (or a struct around acc) compiles to different code.
+template <int N>
+__device__ __forceinline__ void pair_add(double (&acc)[N], int q, double x)
+{
+    acc[2 * q] += x, acc[2 * q + 1] = __builtin_fma(x, x, acc[2 * q + 1]);
+}
+template <int N>
+__device__ __forceinline__ void pair_publish(tail_ptr t, const double (&acc)[N], int q, uint32_t plane)   // after group_sum2
+{
+    publish_pair(t, plane, acc[2 * q], acc[2 * q + 1]);
+}
+
 // the usual end of a kernel with one (sum, sum2) pair per workgroup
 __device__ __forceinline__ void finish_group(double s, double q)
 {

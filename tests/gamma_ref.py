@@ -1,8 +1,8 @@
 """Independent float64 reference of the second-order Greeks estimators (not a test module).
 
 Written from the model: the mixed estimator (Glasserman 7.3, the likelihood-ratio derivative of the pathwise delta) stated
-above vanilla_greeks2_kernel and basket_gamma_kernel (csrc/mc_kernels.hpp) and in include/mc_mi355x.h, evaluated in float64
-with numpy on a given array of normals (greeks_ref's normal streams: vanilla_normals, basket_normals).
+above vanilla_greeks_kernel (its SECOND_ORDER form) and basket_gamma_kernel (csrc/mc_kernels.hpp) and in include/mc_mi355x.h,
+evaluated in float64 with numpy on a given array of normals (greeks_ref's normal streams: vanilla_normals, basket_normals).
 
 Every function returns a greeks_ref `Paths` (value, scale, jump, edge), so that greeks_ref.bound turns it into per-path bounds:
   vanilla_greeks2  rows price, delta, vega, gamma, vanna

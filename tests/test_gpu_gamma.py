@@ -1,4 +1,4 @@
-"""The second-order Greeks kernels (vanilla_greeks2_kernel, basket_gamma_kernel) against the independent float64 reference
+"""The second-order Greeks kernels (vanilla_greeks_kernel's SECOND_ORDER form, basket_gamma_kernel) against the independent float64 reference
 gamma_ref.py on the kernels' own normals (Engine.normals), one path at a time and through many trips, workgroups, tiles and the
 2^32-unit seam; against the first-order kernels' bits; against Black-Scholes; and their refusals.
 
