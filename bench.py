@@ -25,16 +25,21 @@ and timed_region_s are the MEDIAN region's (min / max / all regions reported bes
 over RCCL the barrier that closes a region is the all-reduce of its last bucket of triples (an
 all-reduce is a barrier; --closing barrier adds a separate dist.barrier()).
 
-OUTPUT.  stdout carries ONE line: a JSON object of at most 4096 bytes -- the contract fields, `config`, `roofline`,
-`cpu_baseline`, `fp64`, `configs` (BASELINE configs[1..4] with their roofline fractions and the reference's CPU path), `strong_summary` and,
-at N > 1, the roster of ranks (`ranks`) -- built by
+PLAIN RUN AND --full.  A plain run does what the headline needs and nothing else: it sets up, pre-heats, warms up, times
+the regions, writes --dump-outputs and prints the line.  --full measures, after the timed regions, everything else the
+record below describes: the kernel alone and the roofline, the fp64 side figure, the strong-scaling rows, the CPU
+baselines, BASELINE configs[2..4] and the C library's multi-GPU path.  The timed steps are the same in both.
+
+OUTPUT.  stdout carries ONE line: a JSON object of at most 4096 bytes -- the contract fields, `config`, and with --full
+`roofline`, `cpu_baseline`, `fp64`, `configs` (BASELINE configs[1..4] with their roofline fractions and the reference's CPU path),
+`strong_summary`; at N > 1 the roster of ranks (`ranks`) -- built by
 compact_line() from the full record.  The full record (every strong row, every line of the C library's child process,
 host-side timings, the prose that explains each field) goes to --detail-file (default bench_detail.json next to this
 script; the line names it as `detail`), never to stdout or stderr.  (Round 4's line had grown to 32 KB and the driver
-could not parse it.)  --detail full adds the rows that --detail brief (default) leaves out: the x10 sizes on fp32 normals,
-shard 0 of 2 and of 4, the -O0 build of the reference's CPU path.
+could not parse it.)  With --full, --detail full adds the rows that --detail brief (default) leaves out: the x10 sizes on
+fp32 normals, shard 0 of 2 and of 4, the -O0 build of the reference's CPU path.
 
-In the full record, besides the contract fields:
+In the record of a --full run, besides the contract fields:
   roofline      dominant kernel (the simulation kernel): achieved = algorithmic flop per launch (SURVEY 8d:
                 15.5 flop/path vanilla, n^2+12.5n+6 basket, 60/path-step CVA) / its launch duration, measured live
                 with HIP events bound to the dispatch over 50 launches one at a time right after the timed region
@@ -803,7 +808,8 @@ def configs_summary(detail):
 
 
 def compact_line(detail, detail_name="bench_detail.json"):
-    """The ONE stdout line: contract fields + config + roofline + cpu_baseline + fp64 + strong_summary (+ roster), floats at
+    """The ONE stdout line: contract fields + config (+ what a --full run adds: roofline, cpu_baseline, fp64, configs,
+    strong_summary) (+ roster), floats at
     6 significant digits (value / ms_per_step / timed_region_s in full), at most LINE_LIMIT bytes.  Pure function of the
     full record, so that a CPU test can bound its size from a recorded fixture (tests/test_bench_cli.py)."""
     d = detail
@@ -818,19 +824,20 @@ def compact_line(detail, detail_name="bench_detail.json"):
         line["config"]["rng"] = "Philox4x32-10, counter = path index"
     line.update(_pick(d, "timed_region_s", "regions"))
     body = _pick(d, "ms_per_step_min", "ms_per_step_max", "price", "confidence_95", "paths_priced", "price_error_vs_black_scholes")
-    r = d.get("roofline") or {}
-    roof = _pick(r, "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_stale", "kernel", "avg_kernel_us",
-                 "issue_frac", "issue_frac_at_measured_clock", "sclk_mhz", "hbm_gbps", "grid_workgroups")
-    roof.setdefault("traffic", None)
-    if r.get("in_region"):
-        roof["in_region"] = _pick(r["in_region"], "avg_kernel_us", "concurrent_launches", "step_period_us")
-    if r.get("effective"):
-        roof["effective"] = _pick(r["effective"], "achieved", "frac")
-    if r.get("issue_model"):
-        roof["issue_model"] = _pick(r["issue_model"], "ceiling_us", "frac_effective", "valu_insts_per_path", "valu_busy_long_launch")
-    elif r.get("issue_model_withheld"):
-        roof["issue_model"] = "withheld: committed counters do not describe this build"
-    body["roofline"] = roof
+    r = d.get("roofline")
+    if r:
+        roof = _pick(r, "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_stale", "kernel", "avg_kernel_us",
+                     "issue_frac", "issue_frac_at_measured_clock", "sclk_mhz", "hbm_gbps", "grid_workgroups")
+        roof.setdefault("traffic", None)
+        if r.get("in_region"):
+            roof["in_region"] = _pick(r["in_region"], "avg_kernel_us", "concurrent_launches", "step_period_us")
+        if r.get("effective"):
+            roof["effective"] = _pick(r["effective"], "achieved", "frac")
+        if r.get("issue_model"):
+            roof["issue_model"] = _pick(r["issue_model"], "ceiling_us", "frac_effective", "valu_insts_per_path", "valu_busy_long_launch")
+        elif r.get("issue_model_withheld"):
+            roof["issue_model"] = "withheld: committed counters do not describe this build"
+        body["roofline"] = roof
     if d.get("cpu_baseline"):
         c = d["cpu_baseline"]
         body["cpu_baseline"] = _pick(c, "value", "unit", "cores", "kind", "host_cpus_granted", "value_at_O0")
@@ -889,15 +896,19 @@ def main():
                          "20-step region is 1 ms, one sample of it moves by +-4 %% between runs.  Default 1: exactly K timed steps")
     ap.add_argument("--workload", default="vanilla_f32")
     ap.add_argument("--paths", type=int, default=0, help="paths per GPU per step (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also measure everything besides the headline: the kernel alone and the roofline, "
+                         "the fp64 side figure, the strong-scaling rows, the CPU baselines, BASELINE configs[2..4], the C library's "
+                         "multi-GPU path.  The options marked [--full] tune these and do nothing without it")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
-                    help="CPU baseline sample length of the headline workload (0 = skip every CPU baseline); the other configs' CPU paths "
-                         "run for 2 s each")
+                    help="[--full] CPU baseline sample length of the headline workload (0 = skip every CPU baseline); the other configs' "
+                         "CPU paths run for 2 s each")
     ap.add_argument("--configs", type=int, default=1,
-                    help="1 (default): N = 1 also measures BASELINE configs[2..4] (C3 basket n=4 fp32, C4 basket n=16 fp64 1e9 paths, C5 CVA "
-                         "256 x 1e7 fp64) with roofline fractions, price error and the reference's CPU path beside each; 0 = skip")
+                    help="[--full] 1 (default): N = 1 also measures BASELINE configs[2..4] (C3 basket n=4 fp32, C4 basket n=16 fp64 1e9 "
+                         "paths, C5 CVA 256 x 1e7 fp64) with roofline fractions, price error and the reference's CPU path beside each; 0 = skip")
     ap.add_argument("--detail", default="brief", choices=["brief", "full"],
-                    help="brief (default): strong rows C4, C5, their 10x sizes, C4 / C5 on fp32 normals, shard 0 of 8 -- the driver's run "
-                         "stays under a minute.  full: also the 10x sizes on fp32 normals, shard 0 of 2 and of 4, the -O0 CPU build")
+                    help="[--full] brief (default): strong rows C4, C5, their 10x sizes, C4 / C5 on fp32 normals, shard 0 of 8.  "
+                         "full: also the 10x sizes on fp32 normals, shard 0 of 2 and of 4, the -O0 CPU build")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where rank 0 writes the full record (every row; the stdout line carries the summary and names this file)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -916,9 +927,9 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default). gloo = rehearsal of the multi-rank logic on a box with fewer "
                          "GPUs than ranks: ranks share GPUs (LOCAL_RANK mod device count), triples are reduced on the host")
-    ap.add_argument("--fp64-steps", type=int, default=300, help="steps of the fp64 side measurement (0 = skip)")
+    ap.add_argument("--fp64-steps", type=int, default=300, help="[--full] steps of the fp64 side measurement (0 = skip)")
     ap.add_argument("--exclusive-launches", type=int, default=50,
-                    help="after the timed region, this many launches one at a time on one stream, each timed on the device: "
+                    help="[--full] after the timed region, this many launches one at a time on one stream, each timed on the device: "
                          "the kernel's duration without a neighbour (roofline.exclusive); 0 = skip")
     ap.add_argument("--finish", default="fused", choices=["fused", "kernel"],
                     help="fused (default): the last workgroup of a call adds the per-workgroup pairs inside the simulation "
@@ -928,13 +939,13 @@ def main():
                          "run at the GPU's sustained clock (a cold MI355X needs tens of ms of load to ramp; with --warmup 5 "
                          "the timed region would otherwise measure the ramp).  Reported as config.preheat_ms; 0 = off")
     ap.add_argument("--strong-reps", type=int, default=10,
-                    help="timed calls of each strong-scaling row (C4, C5, 10x sizes, and the same on fp32 normals, sharded over the N "
-                         "ranks; SURVEY 8d: median of >= 10; 0 = skip the block)")
+                    help="[--full] timed calls of each strong-scaling row (C4, C5, 10x sizes, and the same on fp32 normals, sharded over "
+                         "the N ranks; SURVEY 8d: median of >= 10; 0 = skip the block)")
     ap.add_argument("--strong-preheat-ms", type=float, default=300.0,
-                    help="device load before every strong-scaling row (this rank's own shard, back to back), so that T(1) and "
+                    help="[--full] device load before every strong-scaling row (this rank's own shard, back to back), so that T(1) and "
                          "T(shard) are both measured at the sustained clock; 0 = off")
     ap.add_argument("--c-multi-seconds", type=int, default=150,
-                    help="N=1 only: time limit of the child process drivers/multiBench (the C library's own multi-GPU path over "
+                    help="[--full] N=1 only: time limit of the child process drivers/multiBench (the C library's own multi-GPU path over "
                          "1, 2, 4, 8 ... of the visible GPUs); 0 = skip")
     ap.add_argument("--poll", type=int, default=0,
                     help="1: the host polls the launch streams (mc_context_idle) before the closing synchronize of the timed "
@@ -1100,7 +1111,9 @@ def main():
     for i in range(W):
         step(i)
     drain()
-    eng.profile(1 if K < 20 else args.profile_every)   # short regions: every launch of the first context is sampled
+    # short regions: every launch of the first context is sampled.  The samples feed only --full's roofline, but a plain run
+    # takes them too, so that both time the same steps
+    eng.profile(1 if K < 20 else args.profile_every)
     # R timed regions of exactly K steps each, back to back: barrier + synchronize, K steps, drain, barrier + synchronize,
     # MAX over ranks -- the contract's bracket, repeated.  ms_per_step / value come from the MEDIAN region.
     region_s, host_sides = [], []
@@ -1137,7 +1150,7 @@ def main():
     exclusive = None
     my_pci = mc.pci_bus_id(local)
     sclk_headline = None
-    if args.exclusive_launches > 0:
+    if args.full and args.exclusive_launches > 0:
         # the clock the card holds while this kernel runs back to back (amdgpu hwmon, sampled by a side thread): the exclusive
         # launches below follow at once, in that state
         clk_out = torch.zeros((len(engines), 3), dtype=torch.float64, device="cuda")
@@ -1163,7 +1176,7 @@ def main():
     # BASELINE.json's metric names both precisions: the same step in fp64, measured after (and
     # outside) the headline region, reported as a side figure.
     fp64_side = None
-    if args.workload == "vanilla_f32" and args.fp64_steps > 0:
+    if args.full and args.workload == "vanilla_f32" and args.fp64_steps > 0:
         s64 = [e.prepared("vanilla", "f64", VAN)[0] for e in engines]
         side = torch.zeros((args.fp64_steps + 5, 3), dtype=torch.float64, device="cuda")
 
@@ -1196,7 +1209,7 @@ def main():
                      "workload": "same option and path count, fp64 simulation (vanilla_kernel<f64>)"}
 
     strong = None
-    if args.strong_reps > 0 and args.workload == "vanilla_f32":
+    if args.full and args.strong_reps > 0 and args.workload == "vanilla_f32":
         strong = strong_scaling_block(mc, torch, dist, eng, stream, rank, world, grouped, args.backend, barrier,
                                       args.strong_reps, args.strong_preheat_ms, full=args.detail == "full")
 
@@ -1230,31 +1243,7 @@ def main():
             dump_outputs(mc, args.dump_outputs, triples[W + R * K - 1].cpu().tolist(), disc, settings, inputs, X)
         units_per_step = step_total
         value = units_per_step * K / elapsed
-        # ---- roofline of the dominant kernel (the simulation kernel) -------------------------------------------
-        # Durations, all measured live with HIP events bound to the kernel's own dispatch on its launch stream:
-        #   exclusive   n launches one at a time after the timed region: the kernel's duration -> achieved / frac
-        #   in_region   sampled launches inside the timed region; with S streams S launches are co-resident and
-        #               share the machine, so this is NOT a per-kernel duration (kept for the record)
-        #   effective   one GPU's flop per step / the step period: what the whole job sustains per GPU
-        peak = PEAK_TFLOPS[X]
-        flop_launch = flop_per_path * shard_count
-        in_region_s = (kernel_ms_total / samples) * 1e-3 if samples else None
-        ex_n, ex_s = exclusive if exclusive else (0, None)
-        kernel_s = ex_s or in_region_s
-        ach = flop_launch / kernel_s / 1e12 if kernel_s else None
         step_s = elapsed / K
-        committed = {}
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            try:
-                committed = json.load(open(pmc)).get(args.workload, {})
-            except Exception:
-                committed = {}
-        # the committed counts describe launches of one device code object and one launch shape: stale once either changes
-        # (launch_stamp), or when the grid this run launched differs from the grid the PMC passes ran
-        stamp = launch_stamp()
-        grid_mismatch = bool(committed) and live_grid is not None and committed.get("grid_workgroups") not in (None, live_grid)
-        traffic_stale = bool(committed) and (committed.get("launch_stamp") != stamp["stamp"] or grid_mismatch)
         out = {
             "metric": "Monte Carlo paths/sec", "value": value, "unit": "paths/s", "n_gpus": world, "steps": K,
             "warmup": W, "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": args.scaling,
@@ -1272,60 +1261,85 @@ def main():
                                           "(a barrier by construction) + torch.cuda.synchronize" if closing_is_collective else
                                           "barrier + torch.cuda.synchronize on both sides"), **({"engine_settings": settings} if settings else {})},
             "price": price, "confidence_95": ci, "paths_priced": int(tot[2]),
-            "roofline": {"bound": "valu", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                         "frac": (ach / peak) if ach else None,
-                         "traffic": committed.get("hbm_bytes_per_launch"), "traffic_stale": traffic_stale,
-                         "launch_stamp": stamp["stamp"][:16], "grid_workgroups": live_grid, "pmc_grid_workgroups": committed.get("grid_workgroups"),
-                         "hbm_gbps": (committed["hbm_bytes_per_launch"] * shard_count / committed.get("paths_per_launch", shard_count)
-                                      / kernel_s / 1e9) if committed.get("hbm_bytes_per_launch") and kernel_s else None,
-                         "hbm_frac_of_8TBps": (committed["hbm_bytes_per_launch"] * shard_count / committed.get("paths_per_launch", shard_count)
-                                               / kernel_s / 8e12) if committed.get("hbm_bytes_per_launch") and kernel_s else None,
-                         "traffic_source": (committed.get("source", "") + " (committed PMC profile, not measured in this run)")
-                         if committed else None,
-                         "kernel": kernel_name(prod, X, inputs) + (" [antithetic]" if settings.get("antithetic") else " [control variate]" if settings.get("control_variate") else ""),
-                         "flop_per_path": flop_per_path,
-                         "avg_kernel_us": kernel_s * 1e6 if kernel_s else None, "kernel_samples": ex_n if ex_s else samples,
-                         "kernel_paths_per_s": shard_count / kernel_s if kernel_s else None,
-                         "duration_basis": "exclusive: %d launches of the same kernel on the same inputs, one at a time on one "
-                                           "stream right after the timed region, each timed on the device by HIP events bound to "
-                                           "its dispatch" % ex_n if ex_s else "in-region samples (no exclusive phase was run)",
-                         "in_region": {"avg_kernel_us": in_region_s * 1e6 if in_region_s else None, "kernel_samples": samples,
-                                       "concurrent_launches": len(engines), "step_period_us": step_s * 1e6,
-                                       "note": "launches of different streams are co-resident and share the CUs: a launch lasts "
-                                               "about `concurrent_launches` step periods; not a per-kernel duration"},
-                         "effective": {"achieved": flop_launch / step_s / 1e12, "frac": flop_launch / step_s / 1e12 / peak,
-                                       "paths_per_s_per_gpu": shard_count / step_s,
-                                       "note": "flop of one GPU's step / step period (whole job, launch gaps and tails included)"}},
         }
-        if traffic_stale:
-            out["roofline"]["traffic_stale_note"] = ("the device code object, the launch-shape rules (csrc/mc_launch_shape.hpp), HIPFLAGS or the "
-                                                     "launched grid changed since profiles/pmc_traffic.json was collected (tools/collect_pmc_all.sh): "
-                                                     "traffic is the old launches', issue_frac is withheld")
-        # SURVEY 8d's second fraction (issue_ceiling above): at the chip's peak clock and at the clock measured during this run
-        out["roofline"].update(issue_ceiling(args.workload, shard_count, kernel_s, step_s, stamp, traffic_stale, committed, sclk_headline) or {})
-        if sclk_headline and "sclk_mhz" not in out["roofline"]:
-            out["roofline"]["sclk_mhz"] = sclk_headline
         if prod == "vanilla":
             out["price_error_vs_black_scholes"] = abs(price - BS_EXACT)
-        if fp64_side:
-            out["fp64"] = fp64_side
-        if strong:
-            out["strong"] = strong
-        if world == 1 and args.cpu_seconds > 0:
-            out["cpu_baseline"] = cpu_baseline(prod, X, inputs, args.cpu_seconds, full=args.detail == "full")
-            if prod == "vanilla" and X == "f32":
-                extra = cpu_all_cores(1.5)
-                if extra:
-                    out["cpu_all_cores"] = extra
-        if world == 1 and args.workload == "vanilla_f32" and args.configs:
-            # BASELINE.json names five configs: configs[0] is the CPU run (tests), the other four are measured here, one GPU
-            out["configs"] = configs_block(mc, torch, engines, launch_streams, my_pci, out, strong, stamp,
-                                           cpu_seconds=min(2.0, args.cpu_seconds) if args.cpu_seconds > 0 else 0.0)
-        if world == 1 and args.c_multi_seconds > 0 and args.workload == "vanilla_f32":
-            for e in engines:       # the child process gets the GPU to itself
-                e.close()
-            engines = []
-            out["c_multi"] = c_multi_block(args.c_multi_seconds, full=args.detail == "full")
+        if args.full:
+            # ---- roofline of the dominant kernel (the simulation kernel) -------------------------------------------
+            # Durations, all measured live with HIP events bound to the kernel's own dispatch on its launch stream:
+            #   exclusive   n launches one at a time after the timed region: the kernel's duration -> achieved / frac
+            #   in_region   sampled launches inside the timed region; with S streams S launches are co-resident and
+            #               share the machine, so this is NOT a per-kernel duration (kept for the record)
+            #   effective   one GPU's flop per step / the step period: what the whole job sustains per GPU
+            peak = PEAK_TFLOPS[X]
+            flop_launch = flop_per_path * shard_count
+            in_region_s = (kernel_ms_total / samples) * 1e-3 if samples else None
+            ex_n, ex_s = exclusive if exclusive else (0, None)
+            kernel_s = ex_s or in_region_s
+            ach = flop_launch / kernel_s / 1e12 if kernel_s else None
+            committed = {}
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                try:
+                    committed = json.load(open(pmc)).get(args.workload, {})
+                except Exception:
+                    committed = {}
+            # the committed counts describe launches of one device code object and one launch shape: stale once either changes
+            # (launch_stamp), or when the grid this run launched differs from the grid the PMC passes ran
+            stamp = launch_stamp()
+            grid_mismatch = bool(committed) and live_grid is not None and committed.get("grid_workgroups") not in (None, live_grid)
+            traffic_stale = bool(committed) and (committed.get("launch_stamp") != stamp["stamp"] or grid_mismatch)
+            out["roofline"] = {"bound": "valu", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                               "frac": (ach / peak) if ach else None,
+                               "traffic": committed.get("hbm_bytes_per_launch"), "traffic_stale": traffic_stale,
+                               "launch_stamp": stamp["stamp"][:16], "grid_workgroups": live_grid, "pmc_grid_workgroups": committed.get("grid_workgroups"),
+                               "hbm_gbps": (committed["hbm_bytes_per_launch"] * shard_count / committed.get("paths_per_launch", shard_count)
+                                            / kernel_s / 1e9) if committed.get("hbm_bytes_per_launch") and kernel_s else None,
+                               "hbm_frac_of_8TBps": (committed["hbm_bytes_per_launch"] * shard_count / committed.get("paths_per_launch", shard_count)
+                                                     / kernel_s / 8e12) if committed.get("hbm_bytes_per_launch") and kernel_s else None,
+                               "traffic_source": (committed.get("source", "") + " (committed PMC profile, not measured in this run)")
+                               if committed else None,
+                               "kernel": kernel_name(prod, X, inputs) + (" [antithetic]" if settings.get("antithetic") else " [control variate]" if settings.get("control_variate") else ""),
+                               "flop_per_path": flop_per_path,
+                               "avg_kernel_us": kernel_s * 1e6 if kernel_s else None, "kernel_samples": ex_n if ex_s else samples,
+                               "kernel_paths_per_s": shard_count / kernel_s if kernel_s else None,
+                               "duration_basis": "exclusive: %d launches of the same kernel on the same inputs, one at a time on one "
+                                                 "stream right after the timed region, each timed on the device by HIP events bound to "
+                                                 "its dispatch" % ex_n if ex_s else "in-region samples (no exclusive phase was run)",
+                               "in_region": {"avg_kernel_us": in_region_s * 1e6 if in_region_s else None, "kernel_samples": samples,
+                                             "concurrent_launches": len(engines), "step_period_us": step_s * 1e6,
+                                             "note": "launches of different streams are co-resident and share the CUs: a launch lasts "
+                                                     "about `concurrent_launches` step periods; not a per-kernel duration"},
+                               "effective": {"achieved": flop_launch / step_s / 1e12, "frac": flop_launch / step_s / 1e12 / peak,
+                                             "paths_per_s_per_gpu": shard_count / step_s,
+                                             "note": "flop of one GPU's step / step period (whole job, launch gaps and tails included)"}}
+            if traffic_stale:
+                out["roofline"]["traffic_stale_note"] = ("the device code object, the launch-shape rules (csrc/mc_launch_shape.hpp), HIPFLAGS or the "
+                                                         "launched grid changed since profiles/pmc_traffic.json was collected (tools/collect_pmc_all.sh): "
+                                                         "traffic is the old launches', issue_frac is withheld")
+            # SURVEY 8d's second fraction (issue_ceiling above): at the chip's peak clock and at the clock measured during this run
+            out["roofline"].update(issue_ceiling(args.workload, shard_count, kernel_s, step_s, stamp, traffic_stale, committed, sclk_headline) or {})
+            if sclk_headline and "sclk_mhz" not in out["roofline"]:
+                out["roofline"]["sclk_mhz"] = sclk_headline
+            if fp64_side:
+                out["fp64"] = fp64_side
+            if strong:
+                out["strong"] = strong
+            if world == 1 and args.cpu_seconds > 0:
+                out["cpu_baseline"] = cpu_baseline(prod, X, inputs, args.cpu_seconds, full=args.detail == "full")
+                if prod == "vanilla" and X == "f32":
+                    extra = cpu_all_cores(1.5)
+                    if extra:
+                        out["cpu_all_cores"] = extra
+            if world == 1 and args.workload == "vanilla_f32" and args.configs:
+                # BASELINE.json names five configs: configs[0] is the CPU run (tests), the other four are measured here, one GPU
+                out["configs"] = configs_block(mc, torch, engines, launch_streams, my_pci, out, strong, stamp,
+                                               cpu_seconds=min(2.0, args.cpu_seconds) if args.cpu_seconds > 0 else 0.0)
+            if world == 1 and args.c_multi_seconds > 0 and args.workload == "vanilla_f32":
+                for e in engines:       # the child process gets the GPU to itself
+                    e.close()
+                engines = []
+                out["c_multi"] = c_multi_block(args.c_multi_seconds, full=args.detail == "full")
         # the participants ("did RCCL see N ranks?" must be answerable from the record)
         out["world_size"] = dist.get_world_size() if grouped else 1
         out["backend"] = (dist.get_backend() if grouped else "none (single process)")
@@ -1340,7 +1354,8 @@ def main():
         else:
             out["devices_visible"] = torch.cuda.device_count()
             out["device"] = {"index": local, "pci": me["pci"], "name": eng_info["name"], "compute_units": eng_info["compute_units"]}
-        out["config"]["detail"] = args.detail
+        if args.full:
+            out["config"]["detail"] = args.detail
         detail_name = os.path.relpath(args.detail_file, ROOT) if os.path.abspath(args.detail_file).startswith(ROOT + os.sep) else args.detail_file
         line = compact_line(out, detail_name)
         try:

@@ -23,7 +23,7 @@
  *
  *   multiBench [--reps R] [--max-devices G] [--small] [--events] [--no-cold] [--no-n32] [--brief] [--preheat-ms MS]
  *              (--small: 1/100 of the sizes and no pre-heat, for tests;
- *               --brief: what bench.py's default run embeds -- the base sizes only (C4, C5, and both on fp32 normals), shard 0
+ *               --brief: what bench.py --full embeds -- the base sizes only (C4, C5, and both on fp32 normals), shard 0
  *               of 8 only, and the G = 1 handle re-used for the shard rows: one RCCL communicator set-up instead of two)
  */
 #include <unistd.h>

@@ -94,6 +94,26 @@ def test_compact_line_of_the_recorded_round_4_run_fits_4096_bytes():
     assert len(ss["C4x10"]) == 3          # the 10x sizes are measured hot only
 
 
+def test_compact_line_of_a_plain_run_carries_the_headline_only():
+    """A run without --full records no roofline, fp64 side figure, strong rows, CPU baselines, configs or C library rows: its line
+    carries the contract fields and config in full precision, and nothing in place of what was not measured."""
+    import bench
+    d = _fixture6()
+    for k in ("roofline", "fp64", "strong", "cpu_baseline", "cpu_all_cores", "configs", "c_multi"):
+        d.pop(k, None)
+    d["config"].pop("detail", None)
+    line = bench.compact_line(d, "bench_detail.json")
+    assert len(json.dumps(line)) <= 4096 and "dropped_for_size" not in line
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "price", "confidence_95", "paths_priced", "detail"):
+        assert k in line, k
+    assert line["value"] == d["value"] and line["ms_per_step"] == d["ms_per_step"]
+    for k in ("roofline", "fp64", "cpu_baseline", "configs", "strong_summary"):
+        assert k not in line, k
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_compact_line_of_an_eight_rank_run_carries_the_roster_and_fits():
     import bench
     d = _fixture()

@@ -44,7 +44,7 @@ def _port():
 
 def test_bench_contract_single_gpu(tmp_path):
     tmp = tmp_path / "bench_detail.json"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "4", "--regions", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "4", "--regions", "5",
                           "--cpu-seconds", "0.5", "--fp64-steps", "5", "--detail-file", str(tmp)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     assert len(out.stderr) < 2000 and "{" not in out.stderr, out.stderr[-2000:]     # no record on stderr either
@@ -162,7 +162,7 @@ def mc_devices_pow2(visible):
 def test_bench_detail_full_adds_the_rows_brief_leaves_out(tmp_path):
     """--detail full: the 10x sizes on fp32 normals, shard 0 of 2 and of 4, the -O0 CPU build -- short reps here (plumbing)."""
     tmp = tmp_path / "d.json"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--regions", "2", "--cpu-seconds", "0.3",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "2", "--regions", "2", "--cpu-seconds", "0.3",
                           "--fp64-steps", "0", "--strong-reps", "2", "--strong-preheat-ms", "20", "--c-multi-seconds", "0", "--detail", "full",
                           "--detail-file", str(tmp)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -182,7 +182,7 @@ def test_bench_detail_full_adds_the_rows_brief_leaves_out(tmp_path):
 def test_bench_two_ranks_share_the_gpu(scaling, tmp_path):
     tmp = tmp_path / "d.json"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--scaling", scaling,
+           "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--scaling", scaling, "--full",
            "--steps", "30", "--warmup", "3", "--regions", "2", "--cpu-seconds", "0", "--fp64-steps", "4", "--strong-reps", "2", "--strong-preheat-ms", "30",
            "--detail-file", str(tmp)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -237,13 +237,31 @@ def test_bench_steps_and_dumped_outputs(tmp_path):
     assert all((a == b).all() for a, b in zip(*dumps))
 
 
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full a run times its steps and prints the line, and measures nothing else: no kernel-alone launches, no fp64 side
+    figure, no strong rows, no CPU baselines, no configs, no child process.  The contract fields mean what a --full run's do."""
+    tmp = tmp_path / "d.json"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "3", "--detail-file", str(tmp)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = _json_line(out.stdout)
+    d = _detail(line, tmp)
+    assert line["metric"] == "Monte Carlo paths/sec" and line["unit"] == "paths/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["steps"] == 30 and line["warmup"] == 3 and line["regions"] == 1 and line["paths_priced"] == 30 * 10 ** 8
+    assert line["value"] > 1e11 and line["value"] == pytest.approx(10 ** 8 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert abs(d["price"] - BS) < 3.5 / 1.96 * d["confidence_95"]
+    for k in ("roofline", "fp64", "strong", "cpu_baseline", "cpu_all_cores", "configs", "c_multi"):
+        assert k not in d, k
+    assert "detail" not in d["config"] and "strong_summary" not in line
+
+
 def test_bench_rccl_plumbing_world_of_one(tmp_path):
     """The exact launch line the driver uses for N > 1 (torch.distributed.run + RCCL), with one rank:
     process-group creation on the device, bucketed asynchronous all-reduces of the triple rows, the
     device barrier and the MAX over ranks all run through RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "5",
-           "--regions", "5", "--cpu-seconds", "0", "--fp64-steps", "4", "--strong-reps", "2", "--strong-preheat-ms", "30", "--c-multi-seconds", "0",
+           "--regions", "5", "--full", "--cpu-seconds", "0", "--fp64-steps", "4", "--strong-reps", "2", "--strong-preheat-ms", "30", "--c-multi-seconds", "0",
            "--detail-file", str(tmp_path / "d.json")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -271,7 +289,7 @@ def test_bench_two_ranks_rccl_one_rank_per_device(tmp_path):
     tmp = tmp_path / "d.json"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10", "--regions", "3",
-           "--fp64-steps", "20", "--strong-reps", "10", "--detail-file", str(tmp)]
+           "--full", "--fp64-steps", "20", "--strong-reps", "10", "--detail-file", str(tmp)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     print(out.stdout[-5000:])
     assert out.returncode == 0, out.stderr[-3000:]
@@ -298,7 +316,7 @@ def test_bench_four_ranks_share_the_gpu(tmp_path):
     tmp = tmp_path / "d.json"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--steps", "20", "--warmup", "2",
-           "--regions", "2", "--cpu-seconds", "0", "--fp64-steps", "0", "--strong-reps", "2", "--strong-preheat-ms", "20", "--detail-file", str(tmp)]
+           "--regions", "2", "--full", "--cpu-seconds", "0", "--fp64-steps", "0", "--strong-reps", "2", "--strong-preheat-ms", "20", "--detail-file", str(tmp)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = _json_line(out.stdout)

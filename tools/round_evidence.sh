@@ -17,13 +17,13 @@ m = json.load(open("profiles/issue_model.json")); p = json.load(open("profiles/p
 sys.exit(0 if m["vanilla_f32"]["launch_stamp"] == s and p["vanilla_f32"]["launch_stamp"] == s else 1)
 P
 # every bench run: the ONE stdout line (<= 4 KB) into the .log, the full record next to it (--detail-file)
-step "bench default";       python3 bench.py --detail-file $O/${TAG}_bench_detail_default.json > $O/${TAG}_bench_default.log 2>&1
-step "bench detail full";   python3 bench.py --detail full --detail-file $O/${TAG}_bench_detail_full.json > $O/${TAG}_bench_full.log 2>&1
-step "driver style 1";      ( time python3 bench.py --steps 20 --warmup 5 --detail-file $O/${TAG}_bench_detail_driver_style_1.json ) > $O/${TAG}_bench_driver_style_1.log 2>&1
-step "driver style 2";      ( time python3 bench.py --steps 20 --warmup 5 --detail-file $O/${TAG}_bench_detail_driver_style_2.json ) > $O/${TAG}_bench_driver_style_2.log 2>&1
+step "bench default";       python3 bench.py --full --detail-file $O/${TAG}_bench_detail_default.json > $O/${TAG}_bench_default.log 2>&1
+step "bench detail full";   python3 bench.py --full --detail full --detail-file $O/${TAG}_bench_detail_full.json > $O/${TAG}_bench_full.log 2>&1
+step "driver style 1";      ( time python3 bench.py --full --steps 20 --warmup 5 --detail-file $O/${TAG}_bench_detail_driver_style_1.json ) > $O/${TAG}_bench_driver_style_1.log 2>&1
+step "driver style 2";      ( time python3 bench.py --full --steps 20 --warmup 5 --detail-file $O/${TAG}_bench_detail_driver_style_2.json ) > $O/${TAG}_bench_driver_style_2.log 2>&1
 step "all workloads";       bash tools/bench_all.sh > $O/${TAG}_bench_all_workloads.log 2>&1
-step "rocprofv3 default";   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 bench.py --cpu-seconds 0 --strong-reps 0 --c-multi-seconds 0 --configs 0 > $O/${TAG}_rocprofv3_bench_default.log 2>&1
-step "rocprofv3 streams 1"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_streams1 -- python3 bench.py --streams 1 --cpu-seconds 0 --strong-reps 0 --c-multi-seconds 0 --configs 0 > $O/${TAG}_rocprofv3_bench_streams1.log 2>&1
+step "rocprofv3 default";   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 bench.py --full --cpu-seconds 0 --strong-reps 0 --c-multi-seconds 0 --configs 0 > $O/${TAG}_rocprofv3_bench_default.log 2>&1
+step "rocprofv3 streams 1"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_streams1 -- python3 bench.py --full --streams 1 --cpu-seconds 0 --strong-reps 0 --c-multi-seconds 0 --configs 0 > $O/${TAG}_rocprofv3_bench_streams1.log 2>&1
 cp "$(find $O/prof_default -name '*kernel_stats.csv' | tail -1)" $O/${TAG}_rocprofv3_kernel_stats_bench_default.csv
 cp "$(find $O/prof_streams1 -name '*kernel_stats.csv' | tail -1)" $O/${TAG}_rocprofv3_kernel_stats_bench_streams1.csv
 rm -rf $O/prof_default $O/prof_streams1
