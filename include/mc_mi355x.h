@@ -288,6 +288,39 @@ int mc_cva_run_f32(mc_context *ctx, const mc_cva_f32 *cva, uint64_t seed,
 int mc_cva_run_f64(mc_context *ctx, const mc_cva_f64 *cva, uint64_t seed,
                    uint64_t first_path, uint64_t n_paths, mc_result *out);
 
+/* ---- a book of vanilla calls in one launch ----------------------------------------------------
+ * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that
+ * entry's result.  One kernel launch (two with mc_context_set_finish(ctx, 0)) prices the whole book, instead of one launch
+ * per option (about 3.3 us per option at best, the device's dispatch floor).
+ *   - Same sample as a single call: out[i] and mc_vanilla_run_* on entry i's option, seed and range are built from the
+ *     same per-path payoffs, bit for bit (same Philox counters, same per-unit code); only the order in which the sums are
+ *     added may differ (in fp32: which payoffs share an fp32 partial sum before it is added in fp64).  The antithetic switch
+ *     is honoured with the single call's meaning (n counts pairs).
+ *   - An entry's triple depends on that entry alone, bit for bit: not on its index, the other entries, count, the
+ *     context's blocks or which workgroup did the work.  The same book gives the same bits on every call, and the fused
+ *     and the two-launch finish (MC_FINISH=kernel) give the same bits.
+ *   - Philox with native normals only: XORWOW and MC_NORMALS_F32 on the _f64 calls return MC_ERR_UNSUPPORTED.  A book
+ *     never runs on caller-supplied normals (the external-normals test hooks) nor in the reference's launch geometry
+ *     (mc_*_run_grid_*): those are separate entry points, and a context set up for either is refused the same way.
+ *   - Refused with MC_ERR_INVALID before anything is enqueued: count < 1 or > MC_MAX_BOOK, and any entry the single
+ *     call would refuse (n_paths == 0, a range that overflows or needs more than one call, an option out of range);
+ *     mc_last_error names the index of the first bad entry.  Also refused: a book of more than 2^24 chunks in all (an
+ *     entry is at most ~2048 chunks: e.g. more than 8192 entries of 1e8 fp32 paths); the message then names the entry at
+ *     which the count passes the limit, itself valid -- split the book there.  The context stays usable.
+ *   - Timing off (mc_context_set_timing(ctx, 0)): kernel_ms is 0, as for the single calls.
+ *   - kernel_ms and wall_ms are those of the whole book, repeated in every entry; mc_context_last_call_stats describes
+ *     the book call.
+ * The launch form writes the undiscounted {sum, sum2, n} of entry i to d_triples[3 i .. 3 i + 2] (DEVICE memory,
+ * 3 * count doubles), as mc_vanilla_launch_* does for one option.  The book's tables are cached by content: a repeated
+ * book uploads nothing, and its launch may then be captured into a hipGraph. */
+#define MC_MAX_BOOK (1 << 20)
+typedef struct { mc_option_f32 option; uint64_t seed, first_path, n_paths; } mc_book_entry_f32;
+typedef struct { mc_option_f64 option; uint64_t seed, first_path, n_paths; } mc_book_entry_f64;
+int mc_vanilla_book_run_f32(mc_context *ctx, const mc_book_entry_f32 *entries, int count, mc_result *out);
+int mc_vanilla_book_run_f64(mc_context *ctx, const mc_book_entry_f64 *entries, int count, mc_result *out);
+int mc_vanilla_book_launch_f32(mc_context *ctx, const mc_book_entry_f32 *entries, int count, double *d_triples, void *stream);
+int mc_vanilla_book_launch_f64(mc_context *ctx, const mc_book_entry_f64 *entries, int count, double *d_triples, void *stream);
+
 /* ---- pathwise Greeks of the vanilla call (the reference prices only) -------------
  * One pass, the pricing kernels' stream and path indexing: price, delta = dV/dS and vega = dV/dsigma
  * as discounted means of  I (S_T - K),  I S_T / S,  I S_T (sqrt(T) z - sigma T),  I = [S_T > K],

@@ -78,7 +78,17 @@ class CvaGreeks(C.Structure):
     _fields_ = [("cva", Result), ("delta", Result), ("vega", Result)]
 
 
+class BookEntryF32(C.Structure):   # mc_book_entry_f32
+    _fields_ = [("option", OptionF32), ("seed", C.c_uint64), ("first_path", C.c_uint64), ("n_paths", C.c_uint64)]
+
+
+class BookEntryF64(C.Structure):   # mc_book_entry_f64
+    _fields_ = [("option", OptionF64), ("seed", C.c_uint64), ("first_path", C.c_uint64), ("n_paths", C.c_uint64)]
+
+
 OPTION = {"f32": OptionF32, "f64": OptionF64}
+BOOK_ENTRY = {"f32": BookEntryF32, "f64": BookEntryF64}
+MAX_BOOK = 1 << 20   # MC_MAX_BOOK
 BASKET = {"f32": BasketF32, "f64": BasketF64}
 CVA = {"f32": CvaF32, "f64": CvaF64}
 
@@ -98,6 +108,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_vanilla_greeks_run_{_x}", f"mc_vanilla_greeks_lr_run_{_x}", f"mc_basket_greeks_run_{_x}", f"mc_cva_greeks_run_{_x}",
                 f"mc_basket_greeks_lr_run_{_x}", f"mc_cva_greeks_lr_run_{_x}"]
     EXPORTS += [f"mc_vanilla_greeks2_run_{_x}", f"mc_basket_gamma_run_{_x}"]
+    EXPORTS += [f"mc_vanilla_book_run_{_x}", f"mc_vanilla_book_launch_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -168,6 +179,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
                                                                C.POINTER(Result)]
         getattr(L, f"mc_cva_greeks_lr_run_{X}").argtypes = [ctx, C.POINTER(CVA[X]), u64, u64, u64, C.POINTER(CvaGreeks)]
         getattr(L, f"mc_vanilla_greeks2_run_{X}").argtypes = [ctx, C.POINTER(OPTION[X]), u64, u64, u64, C.POINTER(Greeks2)]
+        getattr(L, f"mc_vanilla_book_run_{X}").argtypes = [ctx, C.POINTER(BOOK_ENTRY[X]), C.c_int, C.POINTER(Result)]
+        getattr(L, f"mc_vanilla_book_launch_{X}").argtypes = [ctx, C.POINTER(BOOK_ENTRY[X]), C.c_int, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

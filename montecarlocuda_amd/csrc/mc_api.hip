@@ -116,6 +116,20 @@ struct mc_context {
     bool stats_timed_call = false;   // a timed synchronous call is being enqueued: set-up work that completes on the device re-records ev0
     float create_ms = 0;
     uint64_t sync_calls = 0;
+    // vanilla books (mc_vanilla_book_*): buffers of their own, grown on demand behind quiesce; the tables are cached by content
+    struct Book {
+        void *d_tables = nullptr, *h_tables = nullptr;   // chunk table, entry heads, option constants (h_tables: pinned staging)
+        size_t table_bytes = 0;
+        std::vector<char> key;                           // the bytes now resident in d_tables
+        hipEvent_t copied = nullptr;
+        hipStream_t stream = nullptr;                    // stream of the last upload
+        double2 *d_pairs = nullptr;                      // one pair slot per chunk
+        size_t pair_slots = 0;
+        uint32_t *d_counters = nullptr;                  // ticket words, zero between calls
+        size_t counter_words = 0;
+        double *d_triples = nullptr;                     // 3 per entry (the run form's result buffer)
+        size_t triple_entries = 0;
+    } book;
 };
 
 // Host-clock time of a stage of the call in progress, added to one of the context's accumulators (run_sync reads them).
@@ -218,6 +232,7 @@ static int context_allocate(mc_context *c)
     HIPCHK(hipEventCreate(&c->ev1));
     HIPCHK(hipEventCreateWithFlags(&c->table_copied, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->last_use, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->book.copied, hipEventDisableTiming));
     if (const char *e = getenv("MC_FINISH"))   // "kernel": the two-launch form (A/B baseline); default: fused
         c->fused = strcmp(e, "kernel") != 0;
     if (const char *e = getenv("MC_F64_NORMALS"))   // "f32": the reference's dp arithmetic (mc_context_set_normals)
@@ -331,6 +346,12 @@ extern "C" void mc_context_destroy(mc_context *c)
     (void)hipFree(c->d_ext);
     (void)hipFree(c->d_table);
     (void)hipHostFree(c->h_table);
+    (void)hipFree(c->book.d_tables);
+    (void)hipHostFree(c->book.h_tables);
+    (void)hipFree(c->book.d_pairs);
+    (void)hipFree(c->book.d_counters);
+    (void)hipFree(c->book.d_triples);
+    if (c->book.copied) (void)hipEventDestroy(c->book.copied);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->table_copied) (void)hipEventDestroy(c->table_copied);
@@ -1057,6 +1078,284 @@ static int vanilla_enqueue(mc_context *c, const typename VanillaTraits<Real>::In
         slot += 1;
     }
     return finish_call(c, t, total, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// a book of vanilla calls in one launch (mc_kernels.hpp: vanilla_book_*; mc_launch_shape.hpp: book_plan)
+// ---------------------------------------------------------------------------------------
+template <class Real> struct BookIn;
+template <> struct BookIn<float> { using type = mc_book_entry_f32; };
+template <> struct BookIn<double> { using type = mc_book_entry_f64; };
+
+// A book that passed every check: its plan and the bytes of its device tables -- chunks, entry heads, option constants, in
+// that order (all three 16-byte records).
+struct BookPrepared {
+    BookPlan plan;
+    std::vector<char> tables;
+    size_t heads_at = 0, opts_at = 0;
+    int count = 0;
+};
+
+// Everything that can refuse a book, before anything is enqueued.  A bad entry is one the single call would refuse; the
+// message names the first one.
+template <class Real>
+static int book_prepare(mc_context *c, const typename BookIn<Real>::type *entries, int count, BookPrepared &b)
+{
+    using T = VanillaTraits<Real>;
+    using Opt = typename T::Opt;
+    if (!c) return fail(MC_ERR_INVALID, "NULL context");
+    if (!entries) return fail(MC_ERR_INVALID, "vanilla book: NULL entries");
+    if (count < 1 || count > MC_MAX_BOOK) return fail(MC_ERR_INVALID, "vanilla book: count=%d outside [1, %d]", count, MC_MAX_BOOK);
+    if (c->rng != MC_RNG_PHILOX || c->ext || (sizeof(Real) == 8 && c->normals_f32))
+        return fail(MC_ERR_UNSUPPORTED, "vanilla book: implemented for the Philox generator with native normals only");
+    std::vector<BookHead> heads((size_t)count);
+    std::vector<Opt> opts((size_t)count);
+    int bad_opt = -1;
+    std::string why_opt;
+    for (int i = 0; i < count && bad_opt < 0; ++i) {
+        double scale1, scale2;
+        if (T::prepare(entries[i].option, opts[i], scale1, scale2)) {
+            bad_opt = i;
+            why_opt = mc_last_error();
+            break;
+        }
+        if (c->antithetic && sizeof(Real) == 4)   // as vanilla_enqueue: the fp32 kernels hand back the SUM of the two mirrored payoffs
+            scale1 *= 0.5, scale2 *= 0.25;
+        BookHead &h = heads[i];
+        h.scale1 = scale1, h.scale2 = scale2, h.n_paths = (double)entries[i].n_paths;
+        h.first_path = entries[i].first_path, h.end_path = entries[i].first_path + entries[i].n_paths;
+        h.seed_lo = (uint32_t)entries[i].seed, h.seed_hi = (uint32_t)(entries[i].seed >> 32);
+    }
+    std::vector<BookRange> ranges((size_t)count);
+    for (int i = 0; i < count; ++i)
+        ranges[i] = {entries[i].first_path, entries[i].n_paths};
+    const BookRefusal why = book_plan(ranges.data(), count, (uint32_t)GenPhilox::npb<Real>(), b.plan);
+    if (why != BOOK_OK && (bad_opt < 0 || b.plan.bad_entry < bad_opt)) {
+        static const char *const text[] = {"", "n_paths == 0", "path range overflows 64 bits",
+                                           "n_paths > 2^52 is not exactly representable in the fp64 triple",
+                                           "path range too large for one call (more than 8 segments of 2^31 units); split it",
+                                           "the book has more than 2^24 chunks up to this entry; split the book"};
+        return fail(MC_ERR_INVALID, "vanilla book: entry %d: %s", b.plan.bad_entry, text[why]);
+    }
+    if (bad_opt >= 0)
+        return fail(MC_ERR_INVALID, "vanilla book: entry %d: %s", bad_opt, why_opt.c_str());
+    for (int i = 0; i < count; ++i) {
+        const BookSpan &s = b.plan.spans[i];
+        heads[i].chunk0 = s.chunk0, heads[i].chunks = s.chunks, heads[i].shards = s.shards, heads[i].counter0 = s.counter0;
+    }
+    for (BookChunk &ch : b.plan.chunks)
+        ch.seed_lo = heads[ch.entry].seed_lo, ch.seed_hi = heads[ch.entry].seed_hi;
+    static_assert(sizeof(BookChunk) % 16 == 0 && sizeof(BookHead) % 16 == 0 && sizeof(Opt) % 16 == 0, "16-byte records");
+    const size_t nc = b.plan.chunks.size() * sizeof(BookChunk), nh = heads.size() * sizeof(BookHead), no = opts.size() * sizeof(Opt);
+    b.tables.resize(nc + nh + no);
+    memcpy(b.tables.data(), b.plan.chunks.data(), nc);
+    memcpy(b.tables.data() + nc, heads.data(), nh);
+    memcpy(b.tables.data() + nc + nh, opts.data(), no);
+    b.heads_at = nc, b.opts_at = nc + nh, b.count = count;
+    return MC_OK;
+}
+
+// The book's buffers, at least this large; the ticket words of a new buffer start at zero.  Behind quiesce, as ensure_planes.
+static int book_buffers(mc_context *c, size_t chunks, size_t counter_words, size_t entries)
+{
+    mc_context::Book &k = c->book;
+    if (chunks > k.pair_slots || counter_words > k.counter_words || entries > k.triple_entries)
+        if (int rc = quiesce(c)) return rc;
+    if (chunks > k.pair_slots) {
+        if (k.d_pairs) HIPCHK(hipFree(k.d_pairs));
+        k.d_pairs = nullptr, k.pair_slots = 0;
+        const size_t n = std::max(chunks, (size_t)4096);
+        HIPCHK(hipMalloc(&k.d_pairs, sizeof(double2) * n));
+        k.pair_slots = n;
+    }
+    if (counter_words > k.counter_words) {
+        if (k.d_counters) HIPCHK(hipFree(k.d_counters));
+        k.d_counters = nullptr, k.counter_words = 0;
+        const size_t n = std::max(counter_words, (size_t)4096);
+        HIPCHK(hipMalloc(&k.d_counters, sizeof(uint32_t) * n));
+        HIPCHK(hipMemsetAsync(k.d_counters, 0, sizeof(uint32_t) * n, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        k.counter_words = n;
+    }
+    if (entries > k.triple_entries) {
+        if (k.d_triples) HIPCHK(hipFree(k.d_triples));
+        k.d_triples = nullptr, k.triple_entries = 0;
+        const size_t n = std::max(entries, (size_t)1024);
+        HIPCHK(hipMalloc(&k.d_triples, 3 * sizeof(double) * n));
+        k.triple_entries = n;
+    }
+    return MC_OK;
+}
+
+// The book's tables into HBM, unless the same bytes are already there (cached by content, in a slot of their own: alternating
+// with CVA or generic-basket calls re-uploads neither table).
+static int book_upload(mc_context *c, hipStream_t st, const std::vector<char> &tables)
+{
+    mc_context::Book &k = c->book;
+    if (tables == k.key) {
+        if (st != k.stream)   // uploaded on another stream: order this one behind that upload
+            HIPCHK(hipStreamWaitEvent(st, k.copied, 0));
+        return MC_OK;
+    }
+    StageTimer stage(&c->acc_table_ms);
+    if (tables.size() > k.table_bytes) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (k.stream && k.stream != st) HIPCHK(hipStreamSynchronize(k.stream));
+        if (int rc = quiesce(c)) return rc;   // a launch on another caller stream may still read the old tables
+        if (k.d_tables) HIPCHK(hipFree(k.d_tables));
+        if (k.h_tables) HIPCHK(hipHostFree(k.h_tables));
+        k.d_tables = k.h_tables = nullptr, k.table_bytes = 0, k.key.clear();
+        const size_t n = std::max(tables.size() + tables.size() / 4, (size_t)65536);
+        HIPCHK(hipMalloc(&k.d_tables, n));
+        HIPCHK(hipHostMalloc(&k.h_tables, n, hipHostMallocDefault));
+        k.table_bytes = n;
+    } else {
+        HIPCHK(hipEventSynchronize(k.copied));   // the previous upload has left the staging buffer
+    }
+    k.key.clear();   // until the copy below is enqueued, the device bytes are no longer what the key says
+    memcpy(k.h_tables, tables.data(), tables.size());
+    HIPCHK(hipMemcpyAsync(k.d_tables, k.h_tables, tables.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(k.copied, st));
+    k.stream = st;
+    k.key = tables;
+    return MC_OK;
+}
+
+// Persistent grid: at most `blocks` (fp64: GRID_SCALE_VANILLA_F64 / 2 x blocks) workgroups, as few as give every workgroup the same
+// number of chunks, give or take one.
+static int book_grid(const mc_context *c, size_t chunks, size_t real_bytes)
+{
+    const size_t cap = real_bytes == 8 ? (size_t)c->blocks * GRID_SCALE_VANILLA_F64 / 2 : (size_t)c->blocks;
+    const size_t rounds = (chunks + cap - 1) / cap;
+    return (int)((chunks + rounds - 1) / rounds);
+}
+
+// Enqueue the book on `st`: tables, the simulation kernel, and in the two-launch form the finishing kernel.  Triples go to d_triples.
+template <class Real>
+static int book_enqueue(mc_context *c, const BookPrepared &b, double *d_triples, hipStream_t st)
+{
+    const size_t nch = b.plan.chunks.size();
+    if (int rc = book_buffers(c, nch, b.plan.counter_words, (size_t)b.count)) return rc;
+    if (int rc = book_upload(c, st, b.tables)) return rc;
+    mc_context::Book &k = c->book;
+    const char *base = static_cast<const char *>(k.d_tables);
+    const BookChunk *chunks = reinterpret_cast<const BookChunk *>(base);
+    const BookHead *heads = reinterpret_cast<const BookHead *>(base + b.heads_at);
+    using Opt = typename VanillaTraits<Real>::Opt;
+    const Opt *opts = reinterpret_cast<const Opt *>(base + b.opts_at);
+    const BookOut out = {heads, k.d_pairs, k.d_counters, d_triples, c->fused ? 1u : 0u};
+    const int grid = book_grid(c, nch, sizeof(Real));
+    {
+        ProfileScope prof(c);
+        if constexpr (sizeof(Real) == 4) {
+            launch_sim(prof, c->antithetic ? vanilla_book_f32_kernel<true> : vanilla_book_f32_kernel<false>, grid, st, out, chunks, opts, (uint32_t)nch);
+        } else {
+            launch_sim(prof, c->antithetic ? vanilla_book_kernel<double, true> : vanilla_book_kernel<double, false>, grid, st, out, chunks, opts,
+                       (uint32_t)nch);
+        }
+    }
+    if (!c->fused)
+        vanilla_book_finish_kernel<<<std::min(b.count, c->blocks), GROUP, 0, st>>>(heads, (uint32_t)b.count, k.d_pairs, d_triples);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {   // some chunks may have drawn tickets: put the words back to zero (finish_call)
+        (void)hipStreamSynchronize(st);
+        (void)hipMemsetAsync(k.d_counters, 0, sizeof(uint32_t) * k.counter_words, st);
+        (void)hipStreamSynchronize(st);
+        return fail(MC_ERR_HIP, "vanilla book: kernel launch failed: %s (the book's tickets were reset)", hipGetErrorString(e));
+    }
+    return MC_OK;
+}
+
+template <class Real>
+static int book_launch(mc_context *c, const typename BookIn<Real>::type *entries, int count, double *d_triples, void *stream)
+{
+    BookPrepared b;
+    if (int rc = book_prepare<Real>(c, entries, count, b)) return rc;
+    if (!d_triples) return fail(MC_ERR_INVALID, "vanilla book: NULL output pointer");
+    const hipStream_t st = pick_stream(c, stream);
+    if (int rc = begin_call(c, st)) return rc;
+    return book_enqueue<Real>(c, b, d_triples, st);
+}
+
+// run = enqueue on the context stream, wait, copy every triple back in one copy, close each entry with its own exp(-r t)
+template <class Real>
+static int book_run(mc_context *c, const typename BookIn<Real>::type *entries, int count, mc_result *out)
+{
+    using clock = std::chrono::steady_clock;
+    const auto ms_between = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto wall0 = clock::now();
+    BookPrepared b;
+    if (int rc = book_prepare<Real>(c, entries, count, b)) return rc;
+    if (!out) return fail(MC_ERR_INVALID, "NULL output pointer");
+    c->acc_setup_ms = c->acc_table_ms = 0, c->call_t0_valid = false;
+    c->armed = false;   // as run_sync: a synchronous call cancels mc_context_arm_direct
+    struct Scope {
+        mc_context *c;
+        ~Scope() { c->acc_setup_ms = c->acc_table_ms = 0; }
+    } scope{c};
+    const hipStream_t st = c->stream;
+    if (int rc = begin_call(c, st)) return rc;
+    {
+        StageTimer stage(&c->acc_setup_ms);   // buffer growth is set-up (mc_call_stats)
+        if (int rc = book_buffers(c, b.plan.chunks.size(), b.plan.counter_words, (size_t)count)) return rc;
+    }
+    double *d_triples = c->book.d_triples;
+    // poison (all bits set: NaN): an entry that never closes must not hand back the previous call's triple
+    HIPCHK(hipMemsetAsync(d_triples, 0xFF, 3 * sizeof(double) * (size_t)count, st));
+    if (int rc = book_upload(c, st, b.tables)) return rc;
+    if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));   // timing off (mc_context_set_timing): kernel_ms is reported as 0
+    if (int rc = book_enqueue<Real>(c, b, d_triples, st)) return rc;
+    if (c->timing) HIPCHK(hipEventRecord(c->ev1, st));
+    const auto t_enqueued = clock::now();
+    std::vector<double> h(3 * (size_t)count);
+    HIPCHK(hipMemcpyAsync(h.data(), d_triples, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const auto t_result = clock::now();
+    float ms = 0;
+    if (c->timing) HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    for (int i = 0; i < count; ++i) {
+        const uint64_t n = entries[i].n_paths;
+        if (!(h[3 * i + 2] == (double)n))   // also catches the poison of an entry that never closed
+            return fail(MC_ERR_HIP, "vanilla book: entry %d: device returned n=%g, expected %llu: its final reduction did not complete", i,
+                        h[3 * i + 2], (unsigned long long)n);
+        mc_result &r = out[i];
+        r.sum = h[3 * i], r.sum2 = h[3 * i + 1], r.n = n, r.kernel_ms = ms;
+        const double disc = std::exp(-(double)entries[i].option.r * (double)entries[i].option.t);
+        mc_closing(r.sum, r.sum2, r.n, disc, &r.expected, &r.confidence);
+    }
+    const auto t_closed = clock::now();
+    const float wall = (float)ms_between(wall0, t_closed);
+    for (int i = 0; i < count; ++i)
+        out[i].wall_ms = wall;
+    mc_call_stats &k = c->stats;   // the stage breakdown of the book call (mc_context_last_call_stats), as run_sync
+    const double before = ms_between(wall0, t_enqueued), wait = ms_between(t_enqueued, t_result);
+    k.setup_ms = (float)c->acc_setup_ms;
+    k.table_upload_ms = (float)c->acc_table_ms;
+    k.launch_ms = (float)std::max(0.0, before - c->acc_setup_ms - c->acc_table_ms);
+    k.kernel_ms = (float)std::min((double)ms, wait);
+    k.readback_ms = (float)std::max(0.0, wait - (double)k.kernel_ms);
+    k.closing_ms = (float)ms_between(t_result, t_closed);
+    k.wall_ms = wall;
+    k.context_create_ms = c->create_ms;
+    k.first_call = c->sync_calls++ == 0;
+    return MC_OK;
+}
+
+extern "C" int mc_vanilla_book_run_f32(mc_context *c, const mc_book_entry_f32 *entries, int count, mc_result *out)
+{
+    return book_run<float>(c, entries, count, out);
+}
+extern "C" int mc_vanilla_book_run_f64(mc_context *c, const mc_book_entry_f64 *entries, int count, mc_result *out)
+{
+    return book_run<double>(c, entries, count, out);
+}
+extern "C" int mc_vanilla_book_launch_f32(mc_context *c, const mc_book_entry_f32 *entries, int count, double *d_triples, void *stream)
+{
+    return book_launch<float>(c, entries, count, d_triples, stream);
+}
+extern "C" int mc_vanilla_book_launch_f64(mc_context *c, const mc_book_entry_f64 *entries, int count, double *d_triples, void *stream)
+{
+    return book_launch<double>(c, entries, count, d_triples, stream);
 }
 
 // ---------------------------------------------------------------------------------------

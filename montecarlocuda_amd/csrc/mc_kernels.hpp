@@ -252,6 +252,235 @@ __global__ __launch_bounds__(GROUP) void vanilla_masked_kernel(const Tail /* fir
 }
 
 // =========================================================================================
+// A book of vanilla calls in one launch (mc_vanilla_book_*).  The host (mc_launch_shape.hpp: book_plan) cuts every entry's
+// unit range into CHUNKS: a single-unit masked chunk for a partial first or last unit, and between them chunks of whole units
+// whose boundaries depend on the entry's own range only, none across a multiple of 2^32 units.  A persistent grid walks the
+// chunk table (workgroup x takes chunks x, x + grid, ...); a chunk runs the code of the single call -- the same per-unit
+// function, the hot loop for whole units (fp32: the 8-trip flush), the path-window mask for the edge units -- on 256 lanes,
+// lane t taking units t, t + 256, ..., so its (sum, sum2) pair is the same bits whichever workgroup computes it.  Each chunk
+// publishes its pair into a slot of its own (indexed by chunk) and draws a ticket on its entry's counter; the workgroup that
+// completes an entry adds the entry's pairs in chunk order and writes the entry's triple (book_close).  The two-launch form
+// (fused == 0) stores the pairs plainly and vanilla_book_finish_kernel closes the entries with the same book_close.
+// =========================================================================================
+struct BookChunk {        // 32 bytes: one scalar load
+    uint32_t unit_lo, unit_hi, n_units;
+    uint32_t entry;       // index in the book
+    uint32_t index;       // chunk number within the entry (its ticket shard: index % shards)
+    uint32_t masked;      // 0: whole units; an edge unit: bit j set = path j of the unit is in the entry's range
+    uint32_t seed_lo, seed_hi;   // the entry's seed (the loop reads nothing of the entry but its seed and option constants)
+};
+struct BookHead {         // what the closing needs, and the entry's generator inputs
+    double scale1, scale2, n_paths;   // triple = {scale1 sum, scale2 sum2, n_paths}
+    uint64_t first_path, end_path;    // the entry's range (the masked chunks carry it as a bit mask)
+    uint32_t seed_lo, seed_hi;        // (the chunks carry copies)
+    uint32_t chunk0, chunks;          // the entry's chunks (and pair slots) are chunk0 .. chunk0 + chunks - 1
+    uint32_t shards, counter0;        // ticket words: counter0 (one shard); or shards + 1 words TICKET_STRIDE apart, the top word last
+};
+struct BookOut {          // the FIRST argument of the book kernels, read late (book_out_late) as the Tail is (mc_reduce.hpp: late_tail)
+    const BookHead *heads;   // the entries' heads: read by the closing only
+    double2 *pairs;       // one pair slot per chunk
+    uint32_t *counters;   // all zero between calls (zeroed at allocation, reset by every closer)
+    double *triples;      // 3 doubles per entry
+    uint32_t fused;       // 0: plain pair stores, vanilla_book_finish_kernel follows
+};
+typedef const __attribute__((address_space(4))) BookOut *book_out_t;
+__device__ __forceinline__ book_out_t book_out_late(double after)
+{
+    unsigned long long p = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p) : "v"(after));
+    return (book_out_t)p;
+}
+
+// the Work of a chunk: the entry's seed, the chunk's units
+__device__ __forceinline__ Work book_work(const BookChunk &ch)
+{
+    Work w;
+    w.seed_lo = ch.seed_lo, w.seed_hi = ch.seed_hi;
+    w.unit_lo = ch.unit_lo, w.unit_hi = ch.unit_hi, w.n_units = ch.n_units;
+    w.first_path = w.end_path = 0;   // unused: a masked chunk carries its window as a bit mask
+    w.xorwow = nullptr, w.ext = nullptr, w.ext_per_unit = 0;
+    return w;
+}
+
+// Every lane: the entry's pairs in chunk order (lane t adds pairs t, t + 256, ...), the DPP/LDS reduction, the triple.
+__device__ __forceinline__ void book_close(const double2 *pairs, const BookHead &h, double *triple)
+{
+    double s = 0.0, q = 0.0;
+    for (uint32_t i = threadIdx.x; i < h.chunks; i += GROUP) {
+        const double2 p = pairs[h.chunk0 + i];
+        s += p.x;
+        q += p.y;
+    }
+    group_sum2(s, q);
+    if (threadIdx.x == 0) {
+        triple[0] = h.scale1 * s;
+        triple[1] = h.scale2 * q;
+        triple[2] = h.n_paths;
+    }
+}
+
+// The tables are read through the constant address space (scalar loads: chunk, head and option constants are wave-uniform).  The kernel
+// never writes them; the host uploads them before the launch.
+typedef const __attribute__((address_space(4))) BookChunk *book_chunks_t;
+typedef const __attribute__((address_space(4))) BookHead *book_heads_t;
+// C++ copies no struct out of another address space: field by field (each a scalar load)
+__device__ __forceinline__ BookChunk book_load(book_chunks_t p)
+{
+    return {p->unit_lo, p->unit_hi, p->n_units, p->entry, p->index, p->masked, p->seed_lo, p->seed_hi};
+}
+__device__ __forceinline__ BookHead book_load(book_heads_t p)
+{
+    return {p->scale1, p->scale2, p->n_paths, p->first_path, p->end_path, p->seed_lo, p->seed_hi, p->chunk0, p->chunks, p->shards, p->counter0};
+}
+// After group_sum2 of chunk `ci`: publish its pair and, in the fused form, draw the entry's ticket; the workgroup that completes the
+// entry closes it.  The protocol of arrive_and_finish (mc_reduce.hpp): write-through pair stores -> s_waitcnt vmcnt(0) -> relaxed
+// agent-scope fetch_add on shard index % shards; the arrival that completes its shard adds 1 to the top word (entries of more than
+// one shard), the one that completes that is the closer: agent-scope acquire -> plain loads.  A shard takes at most BOOK_SHARD_CHUNKS
+// arrivals and the top word at most ~BOOK_CHUNKS_MAX / BOOK_SHARD_CHUNKS (mc_launch_shape.hpp).
+__device__ __forceinline__ void book_arrive(uint32_t ci, book_chunks_t chunks, double s, double q)
+{
+    const book_out_t po = book_out_late(s);
+    const BookOut out = {po->heads, po->pairs, po->counters, po->triples, po->fused};
+    const BookChunk ch = book_load(chunks + ci);
+    const BookHead h = book_load((book_heads_t)out.heads + ch.entry);
+    __shared__ uint32_t lds_close;
+    if (threadIdx.x == 0) {
+        if (!out.fused) {
+            out.pairs[ci] = make_double2(s, q);
+        } else {   // write-through: the bytes leave this XCD's L2 (which no other XCD can see into)
+            gu64_t *g = (gu64_t *)(out.pairs + ci);
+            __hip_atomic_store(g, (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(g + 1, (unsigned long long)__double_as_longlong(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the pair stores have left before the ticket is drawn
+            const uint32_t shard = ch.index % h.shards, in_shard = (h.chunks - shard + h.shards - 1) / h.shards;
+            const uint32_t stride = h.shards > 1 ? TICKET_STRIDE : 1;   // the words of a sharded entry: one 128-byte line each
+            gu32_t *k = (gu32_t *)out.counters + h.counter0;
+            uint32_t last = __hip_atomic_fetch_add(k + shard * stride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == in_shard;
+            if (last && h.shards > 1)
+                last = __hip_atomic_fetch_add(k + h.shards * stride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == h.shards;
+            lds_close = last;
+        }
+    }
+    if (!out.fused)
+        return;
+    __syncthreads();
+    if (!lds_close)   // workgroup-uniform
+        return;
+    if (threadIdx.x == 0)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // drop this CU's stale lines of the pair buffer
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    book_close(out.pairs, h, out.triples + 3 * (size_t)ch.entry);
+    if (threadIdx.x < h.shards + (h.shards > 1 ? 1u : 0u))   // ready for the next call
+        __hip_atomic_store((gu32_t *)out.counters + h.counter0 + threadIdx.x * (h.shards > 1 ? TICKET_STRIDE : 1), 0u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A masked chunk (one edge unit) runs the same loop; the payoffs of the paths outside the entry's range are zeroed before they are added.
+template <class Real> __device__ __forceinline__ Real book_window(Real p, uint32_t mask, int j) { return ((mask >> j) & 1u) ? p : (Real)0; }
+
+// fp32: vanilla_f32_kernel's loop (packed pairs, the 8-trip flush), with lanes striding one workgroup
+template <bool ANTI>
+__global__ __launch_bounds__(GROUP) void vanilla_book_f32_kernel(const BookOut /* first argument, read late */, const BookChunk *chunk_table,
+                                                                 const VanillaF32 *__restrict__ opt_table,
+                                                                 uint32_t n_chunks)
+{
+    const book_chunks_t chunks = (book_chunks_t)chunk_table;
+    for (uint32_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
+        const BookChunk ch = book_load(chunks + ci);
+        const VanillaF32 &o = opt_table[ch.entry];   // a reference: a local copy becomes a per-lane LDS array (AMDGPUPromoteAlloca)
+        const Work w = book_work(ch);
+        GenPhilox gen(w);
+        double acc_s = 0.0, acc_q = 0.0;
+        const uint32_t full_trips = w.n_units / GROUP;
+        f2 s2 = {0.0f, 0.0f}, q2 = {0.0f, 0.0f};
+        uint32_t c0 = w.unit_lo + threadIdx.x;
+        for (uint32_t trip = 0; trip < full_trips; ++trip, c0 += GROUP) {
+            f2 pc, ps;
+            vanilla_unit_pk<ANTI>(gen, o, w, c0, pc, ps);
+            s2 += pc;
+            s2 += ps;
+            q2 = pk_fma(pc, pc, q2);
+            q2 = pk_fma(ps, ps, q2);
+            if ((trip & (VANILLA_F32_FLUSH - 1)) == VANILLA_F32_FLUSH - 1) {
+                acc_s += (double)(s2.x + s2.y);
+                acc_q += (double)(q2.x + q2.y);
+                s2 = (f2){0.0f, 0.0f};
+                q2 = (f2){0.0f, 0.0f};
+            }
+        }
+        if (full_trips * GROUP + threadIdx.x < w.n_units) {   // the partial last trip (a masked chunk's one unit)
+            f2 pc, ps;
+            vanilla_unit_pk<ANTI>(gen, o, w, c0, pc, ps);
+            if (ch.masked) {   // an edge unit, as vanilla_masked_kernel adds it: every live path in fp64
+                const float p[4] = {pc.x, ps.x, pc.y, ps.y};   // path order inside the unit: 4q+0 .. 4q+3
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double x = book_window(p[j], ch.masked, j);
+                    acc_s += x;
+                    acc_q += x * x;
+                }
+            } else {
+                s2 += pc + ps;
+                q2 += pc * pc + ps * ps;
+            }
+        }
+        acc_s += (double)(s2.x + s2.y);
+        acc_q += (double)(q2.x + q2.y);
+        group_sum2(acc_s, acc_q);
+        book_arrive(ci, chunks, acc_s, acc_q);
+    }
+}
+
+// fp64: vanilla_kernel's loop, with lanes striding one workgroup; the LDS tables are staged once per workgroup
+template <class Real, bool ANTI>
+__global__ __launch_bounds__(GROUP) void vanilla_book_kernel(const BookOut /* first argument, read late */, const BookChunk *chunk_table,
+                                                             const VanillaF64 *__restrict__ opt_table,
+                                                             uint32_t n_chunks)
+{
+    static_assert(sizeof(Real) == 8, "the fp32 book is vanilla_book_f32_kernel");
+    stage_tables<Real>();
+    constexpr int NPB = GenPhilox::npb<Real>();
+    const book_chunks_t chunks = (book_chunks_t)chunk_table;
+    for (uint32_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
+        const BookChunk ch = book_load(chunks + ci);
+        const VanillaF64 &o = opt_table[ch.entry];   // a reference: a local copy becomes a per-lane LDS array (AMDGPUPromoteAlloca)
+        const Work w = book_work(ch);
+        GenPhilox gen(w);
+        double acc_s = 0.0, acc_q = 0.0;
+        for (uint32_t i = threadIdx.x; i < w.n_units; i += GROUP) {
+            Real p[NPB];
+            vanilla_unit<ANTI>(gen, o, w, w.unit_lo + i, p);
+            if (ch.masked) {   // an edge unit (the chunk's only one)
+#pragma unroll
+                for (int j = 0; j < NPB; ++j)
+                    p[j] = book_window(p[j], ch.masked, j);
+            }
+            Real s = p[0], q = p[0] * p[0];
+#pragma unroll
+            for (int j = 1; j < NPB; ++j) {
+                s += p[j];
+                q = fma_r(p[j], p[j], q);
+            }
+            acc_s += (double)s;
+            acc_q += (double)q;
+        }
+        group_sum2(acc_s, acc_q);
+        book_arrive(ci, chunks, acc_s, acc_q);
+    }
+}
+
+// Two-launch form: workgroup x closes entries x, x + grid, ... from the pairs the simulation kernel stored
+__global__ __launch_bounds__(GROUP) void vanilla_book_finish_kernel(const BookHead *__restrict__ heads, uint32_t count, const double2 *pairs,
+                                                                    double *triples)
+{
+    for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
+        const BookHead h = heads[e];
+        book_close(pairs, h, triples + 3 * (size_t)e);
+    }
+}
+
+// =========================================================================================
 // Vanilla call with its Greeks (the reference prices only).  Per path, on the same normal as the pricing kernels:
 //     S_T = S exp(drift + vol z),   I = [S_T > K],   payoff = I (S_T - K)
 // in one of three forms (GreeksForm):

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/mc_mi355x.h"
 #include "mc_grid.hpp"   // GROUP, GRID_SEG_ALIGN
@@ -170,6 +171,119 @@ static CvaPlan cva_plan(int forced_lanes, uint64_t n, int n_dates, int compute_u
     l = l < 1 ? 1 : (l > max_l ? max_l : l);
     p.main_paths = n - r, p.tail_paths = r, p.log2_lanes = l;
     return p;
+}
+
+// Vanilla books (mc_vanilla_book_*, mc_kernels.hpp vanilla_book_*): the chunks of every entry.  An entry of paths [first, end) in
+// units of `npb` paths gets, in unit order:
+//   * a masked chunk of ONE unit for a partial first unit, and one for a partial last unit (the single call's edge launches): its
+//     `masked` word has bit j set for each path j of the unit inside the entry's range;
+//   * the whole units between them in chunks of max(book_chunk_min, units / BOOK_CHUNKS_MAX rounded up to whole 256-lane trips)
+//     units -- at most ~BOOK_CHUNKS_MAX chunks however large the entry -- also cut at every multiple
+//     of 2^32 units (a chunk's high counter word is wave-uniform).
+// So the boundaries are a function of the entry's own (first, n), precision and estimator: what makes an entry's triple the same
+// bits wherever it sits in a book.  Ticket words: an entry of c chunks draws on s = ceil(c / BOOK_SHARD_CHUNKS) shard words
+// (chunk j on shard j % s, at most BOOK_SHARD_CHUNKS arrivals each) and, when s > 1, on a top word of its own (s arrivals), each word
+// of such an entry on a 128-byte line of its own (TICKET_STRIDE, as arrive_and_finish's tickets): a large entry never serialises
+// thousands of arrivals on one word or line (~11-13 ns each, MI355X_MICROARCH.md "fanin").
+// Refused (the index of the first bad entry is reported): what the single call refuses -- n == 0, a range past 2^64, n > 2^52,
+// more than MAX_SEGMENTS segments of whole units -- and a book of more than BOOK_MAX_CHUNKS chunks in all (the entry named is
+// the one at which the count passes the limit; nothing is stored before that is known).
+constexpr uint32_t BOOK_CHUNKS_MAX = 2048, BOOK_SHARD_CHUNKS = 64;
+// a chunk of whole units is at least what a lane of the single 1e8-path call does on the default grid (fp32 48 units, fp64 16): a
+// chunk pays scalar table loads, a workgroup reduction and a returning agent-scope atomic, which 6 units per lane did not amortise
+// (profiles/book_speed.log: 8 x 1.25e7-path entries +58 % over one 1e8-path call in fp32 with chunks of 6 units per lane)
+static uint64_t book_chunk_min(uint32_t npb) { return (npb == 4 ? 48ull : 16ull) * GROUP; }
+constexpr uint64_t BOOK_MAX_CHUNKS = 1ull << 24;
+struct BookRange { uint64_t first_path, n_paths; };
+struct BookSpan { uint32_t chunk0, chunks, shards, counter0; };
+enum BookRefusal { BOOK_OK, BOOK_EMPTY, BOOK_OVERFLOW, BOOK_TOO_MANY_PATHS, BOOK_TOO_MANY_SEGMENTS, BOOK_TOO_MANY_CHUNKS };
+struct BookPlan {
+    std::vector<BookChunk> chunks;
+    std::vector<BookSpan> spans;   // per entry
+    uint32_t counter_words = 0;
+    int bad_entry = -1;            // the first refused entry
+};
+static uint64_t book_chunk_units(uint64_t units, uint32_t npb)
+{
+    uint64_t c = (units + BOOK_CHUNKS_MAX - 1) / BOOK_CHUNKS_MAX;
+    c = (c + GROUP - 1) / GROUP * GROUP;
+    c = c < book_chunk_min(npb) ? book_chunk_min(npb) : c;
+    return c < (1ull << 31) ? c : (1ull << 31);
+}
+// The chunks of one valid entry, in unit order (emit(unit, units, mask) for each; mask 0 = whole units); returns their count
+template <class Emit>
+static uint32_t book_entry_chunks(uint64_t first, uint64_t n, uint32_t npb, Emit emit)
+{
+    const uint64_t end = first + n, head = first / npb, tail_unit = end / npb, u0 = (first + npb - 1) / npb, u1 = end / npb;
+    const bool has_head = first % npb != 0, has_tail = end % npb != 0 && !(has_head && tail_unit == head);
+    const auto bits = [&](uint64_t unit) {   // the unit's paths inside [first, end)
+        uint32_t m = 0;
+        for (uint32_t j = 0; j < npb; ++j)
+            m |= (unit * npb + j >= first && unit * npb + j < end) ? 1u << j : 0u;
+        return m;
+    };
+    uint32_t count = 0;
+    if (has_head)
+        emit(head, 1, bits(head)), ++count;
+    const uint64_t cu = book_chunk_units(u1 > u0 ? u1 - u0 : 0, npb);
+    for (uint64_t u = u0; u < u1; ++count) {
+        const uint64_t seam = ((u >> 32) + 1) << 32;
+        uint64_t next = u + cu;
+        next = next < u1 ? next : u1;
+        next = next < seam ? next : seam;
+        emit(u, next - u, 0u);
+        u = next;
+    }
+    if (has_tail)
+        emit(tail_unit, 1, bits(tail_unit)), ++count;
+    return count;
+}
+static BookRefusal book_plan(const BookRange *r, int count, uint32_t npb, BookPlan &p)
+{
+    p.chunks.clear(), p.spans.clear(), p.counter_words = 0, p.bad_entry = -1;
+    // first pass: every entry valid, and the book's chunk count within BOOK_MAX_CHUNKS -- before anything is stored
+    uint64_t total = 0;
+    for (int e = 0; e < count; ++e) {
+        const uint64_t first = r[e].first_path, n = r[e].n_paths, end = first + n;
+        BookRefusal why = n == 0 ? BOOK_EMPTY : (end < first ? BOOK_OVERFLOW : (n > (1ull << 52) ? BOOK_TOO_MANY_PATHS : BOOK_OK));
+        const uint64_t u0 = (first + npb - 1) / npb, u1 = end / npb;
+        if (why == BOOK_OK && u1 > u0) {   // plan_segments' rule (mc_api.hip): segments of <= 2^31 units, none across 2^32
+            int segs = 0;
+            for (uint64_t u = u0; u < u1 && segs <= MAX_SEGMENTS; ++segs) {
+                const uint64_t room = (1ull << 32) - (u & 0xFFFFFFFFull), left = u1 - u;
+                uint64_t m = left < room ? left : room;
+                u += m < (1ull << 31) ? m : (1ull << 31);
+            }
+            if (segs > MAX_SEGMENTS)
+                why = BOOK_TOO_MANY_SEGMENTS;
+        }
+        if (why == BOOK_OK) {
+            total += book_entry_chunks(first, n, npb, [](uint64_t, uint64_t, uint32_t) {});
+            if (total > BOOK_MAX_CHUNKS)
+                why = BOOK_TOO_MANY_CHUNKS;
+        }
+        if (why != BOOK_OK) {
+            p.bad_entry = e;
+            return why;
+        }
+    }
+    p.chunks.reserve((size_t)total);
+    p.spans.reserve((size_t)count);
+    for (int e = 0; e < count; ++e) {
+        BookSpan s = {(uint32_t)p.chunks.size(), 0, 0, 0};
+        s.chunks = book_entry_chunks(r[e].first_path, r[e].n_paths, npb, [&](uint64_t unit, uint64_t units, uint32_t mask) {
+            p.chunks.push_back({(uint32_t)unit, (uint32_t)(unit >> 32), (uint32_t)units, (uint32_t)e, (uint32_t)(p.chunks.size() - s.chunk0), mask, 0u, 0u});   // seeds: the caller
+        });
+        s.shards = (s.chunks + BOOK_SHARD_CHUNKS - 1) / BOOK_SHARD_CHUNKS;
+        if (s.shards == 1) {
+            s.counter0 = p.counter_words++;
+        } else {   // shards + 1 words, one 128-byte line each (mc_reduce.hpp TICKET_STRIDE)
+            s.counter0 = (p.counter_words + TICKET_STRIDE - 1) / TICKET_STRIDE * TICKET_STRIDE;
+            p.counter_words = s.counter0 + (s.shards + 1) * TICKET_STRIDE;
+        }
+        p.spans.push_back(s);
+    }
+    return BOOK_OK;
 }
 
 // How many pieces the fused kernels cut every reference thread's stream into (mc_grid.hpp "sub-streams"): enough to put

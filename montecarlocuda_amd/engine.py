@@ -254,6 +254,39 @@ class Engine:
     def vanilla(self, opt, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
         return self._run("vanilla", precision, _as_option(precision, opt), seed, first_path, n_paths)
 
+    @staticmethod
+    def book_entries(options, n_paths, seeds=None, first_paths=None, precision="f64"):
+        """The ctypes array of mc_book_entry_{f32,f64} for a book: n_paths, seeds and first_paths are one value for every
+        option or one per option (seeds default to MC_DEFAULT_SEED, first paths to 0)."""
+        B = len(options)
+
+        def per(x, default):
+            x = default if x is None else x
+            xs = list(x) if isinstance(x, (list, tuple, np.ndarray)) else [x] * B
+            if len(xs) != B:
+                raise ValueError("vanilla_book: one value per option expected")
+            return [int(v) for v in xs]
+        ns, ss, fs = per(n_paths, None), per(seeds, MC_DEFAULT_SEED), per(first_paths, 0)
+        arr = (_lib.BOOK_ENTRY[precision] * B)()
+        for i, o in enumerate(options):
+            arr[i].option = _as_option(precision, o)
+            arr[i].seed, arr[i].first_path, arr[i].n_paths = ss[i], fs[i], ns[i]
+        return arr
+
+    def vanilla_book(self, options, n_paths, seeds=None, first_paths=None, precision="f64"):
+        """A book of vanilla calls priced in one launch (mc_vanilla_book_run_*): one Estimate per option, each from the same
+        per-path payoffs as vanilla(option, n, seed, first_path, precision)."""
+        arr = self.book_entries(options, n_paths, seeds, first_paths, precision)
+        res = (_lib.Result * len(arr))()
+        check(getattr(lib(), f"mc_vanilla_book_run_{precision}")(self._ctx, arr, len(arr), res))
+        return [_estimate(r) for r in res]
+
+    def vanilla_book_launch(self, options, n_paths, d_triples_ptr: int, seeds=None, first_paths=None, precision="f64", stream: int = 0):
+        """Enqueue a book (mc_vanilla_book_launch_*): entry i's undiscounted {sum, sum2, n} into the 3 doubles at
+        d_triples_ptr + 24 i (device memory), on `stream` (0 = the HIP null stream)."""
+        arr = self.book_entries(options, n_paths, seeds, first_paths, precision)
+        check(getattr(lib(), f"mc_vanilla_book_launch_{precision}")(self._ctx, arr, len(arr), C.c_void_p(d_triples_ptr), C.c_void_p(stream)))
+
     def vanilla_greeks(self, opt, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         """(price, delta, vega) Estimates from one pass (pathwise derivatives)."""
         g = _lib.Greeks()
