@@ -45,6 +45,19 @@ using namespace mc;
 // context
 // ---------------------------------------------------------------------------------------
 
+// A device table cached by content: upload() copies the bytes into HBM through a pinned staging buffer unless the bytes resident
+// there were built from the same key, and orders the calling stream behind the copy either way.
+struct CachedTable {
+    const size_t floor_bytes, headroom_div;   // growth: bytes + bytes / headroom_div (0: none), at least floor_bytes
+    void *d = nullptr, *h = nullptr;          // device buffer, pinned staging for it
+    size_t capacity = 0;
+    std::vector<char> key;                    // what the bytes now resident in d were built from
+    hipEvent_t copied = nullptr;
+    hipStream_t stream = nullptr;             // stream of the last upload
+    void destroy();
+    int upload(mc_context *c, hipStream_t st, const std::vector<char> &new_key, const void *data, size_t bytes);
+};
+
 struct mc_context {
     int device = 0;
     int blocks = 0;
@@ -71,13 +84,8 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    void *d_table = nullptr;      // CVA per-date table
-    void *h_table = nullptr;      // pinned staging for it
-    size_t table_bytes = 0;
-    std::vector<char> table_key;  // inputs the cached table was built from
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, a generic basket's folded constants, a basket's Greeks table
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
-    hipEvent_t table_copied = nullptr;
-    hipStream_t table_stream = nullptr;  // stream the cached table was uploaded on
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // generator: Philox (counter-based, stateless) or XORWOW (one sequence per lane: mc_rng.hpp GenXorwow)
     int rng = MC_RNG_PHILOX;
@@ -118,11 +126,7 @@ struct mc_context {
     uint64_t sync_calls = 0;
     // vanilla books (mc_vanilla_book_*): buffers of their own, grown on demand behind quiesce; the tables are cached by content
     struct Book {
-        void *d_tables = nullptr, *h_tables = nullptr;   // chunk table, entry heads, option constants (h_tables: pinned staging)
-        size_t table_bytes = 0;
-        std::vector<char> key;                           // the bytes now resident in d_tables
-        hipEvent_t copied = nullptr;
-        hipStream_t stream = nullptr;                    // stream of the last upload
+        CachedTable tables{65536, 4};                    // chunk table, entry heads, option constants; the key is the bytes themselves
         double2 *d_pairs = nullptr;                      // one pair slot per chunk
         size_t pair_slots = 0;
         uint32_t *d_counters = nullptr;                  // ticket words, zero between calls
@@ -218,6 +222,49 @@ static int quiesce(mc_context *c)
     return MC_OK;
 }
 
+void CachedTable::destroy()
+{
+    (void)hipFree(d);
+    (void)hipHostFree(h);
+    if (copied) (void)hipEventDestroy(copied);
+}
+
+int CachedTable::upload(mc_context *c, hipStream_t st, const std::vector<char> &new_key, const void *data, size_t bytes)
+{
+    if (new_key == key) {
+        if (st != stream)   // uploaded on another stream: order this one behind that upload
+            HIPCHK(hipStreamWaitEvent(st, copied, 0));
+        return MC_OK;
+    }
+    StageTimer stage(&c->acc_table_ms);
+    if (bytes > capacity) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (stream && stream != st) HIPCHK(hipStreamSynchronize(stream));
+        if (int rc = quiesce(c)) return rc;   // a launch on another caller stream may still read the old table
+        // nothing of the old table outlives its buffers: an allocation that fails below leaves an empty table, not a dangling one
+        key.clear(), capacity = 0;
+        if (d) HIPCHK(hipFree(d));
+        d = nullptr;
+        if (h) HIPCHK(hipHostFree(h));
+        h = nullptr;
+        const size_t grown = std::max(bytes + (headroom_div ? bytes / headroom_div : 0), floor_bytes);
+        HIPCHK(hipMalloc(&d, grown));
+        HIPCHK(hipHostMalloc(&h, grown, hipHostMallocDefault));
+        capacity = grown;
+    } else {
+        HIPCHK(hipEventSynchronize(copied));   // the previous upload has left the staging buffer
+    }
+    key.clear();   // until the copy below is enqueued, the device bytes are no longer what the key says
+    if (bytes) {
+        memcpy(h, data, bytes);
+        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipEventRecord(copied, st));
+    stream = st;
+    key = new_key;
+    return MC_OK;
+}
+
 static int context_allocate(mc_context *c)
 {
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -230,9 +277,9 @@ static int context_allocate(mc_context *c)
     HIPCHK(hipHostGetDevicePointer((void **)&c->d_direct, c->h_direct, 0));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
-    HIPCHK(hipEventCreateWithFlags(&c->table_copied, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->table.copied, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->last_use, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->book.copied, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->book.tables.copied, hipEventDisableTiming));
     if (const char *e = getenv("MC_FINISH"))   // "kernel": the two-launch form (A/B baseline); default: fused
         c->fused = strcmp(e, "kernel") != 0;
     if (const char *e = getenv("MC_F64_NORMALS"))   // "f32": the reference's dp arithmetic (mc_context_set_normals)
@@ -344,17 +391,13 @@ extern "C" void mc_context_destroy(mc_context *c)
     (void)hipHostFree(c->h_direct);
     (void)hipFree(c->d_out);
     (void)hipFree(c->d_ext);
-    (void)hipFree(c->d_table);
-    (void)hipHostFree(c->h_table);
-    (void)hipFree(c->book.d_tables);
-    (void)hipHostFree(c->book.h_tables);
+    c->table.destroy();
+    c->book.tables.destroy();
     (void)hipFree(c->book.d_pairs);
     (void)hipFree(c->book.d_counters);
     (void)hipFree(c->book.d_triples);
-    if (c->book.copied) (void)hipEventDestroy(c->book.copied);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->table_copied) (void)hipEventDestroy(c->table_copied);
     for (hipEvent_t e : c->prof_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->prof_stop) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -708,6 +751,105 @@ static int finish_call(mc_context *c, const Tail &t, int total, hipStream_t st)
     return MC_OK;
 }
 
+// A list of segments that is not necessarily a vector (vanilla_enqueue's edge units live on its stack)
+struct Segments {
+    const Segment *first;
+    size_t count;
+    Segments(const std::vector<Segment> &v) : first(v.data()), count(v.size()) {}
+    Segments(const Segment *p = nullptr, size_t n = 0) : first(p), count(n) {}
+    const Segment *begin() const { return first; }
+    const Segment *end() const { return first + count; }
+};
+
+// A multi-plane call (planes_run): `count` planes of `stride` pairs in a buffer of their own; grid_y = workgroups per x position,
+// each of which draws a ticket.  The default is every other call: one plane in the context's pair buffer.
+struct Planes {
+    double2 *pairs = nullptr;
+    int count = 1, stride = 0, grid_y = 1;
+};
+
+// pairs of a call that launches once per segment of `a`, then once per segment of `b`: grid(segment, 0 for a / 1 for b) = workgroups of a launch
+template <class Grid>
+static int call_pairs(Segments a, Segments b, Grid grid)
+{
+    int pairs = 0;
+    for (const Segment &s : a) pairs += grid(s, 0);
+    for (const Segment &s : b) pairs += grid(s, 1);
+    return pairs;
+}
+
+// Enqueues those launches as ONE call: every launch gets the call's Tail with its own position in the pair buffer and the ticket
+// block, and the call is closed behind the last.  launch(tail, segment, workgroups, units of the segments before it, 0 for a / 1 for b).
+template <class Grid, class Launch>
+static int launch_call(mc_context *c, hipStream_t st, double scale1, double scale2, uint64_t n, double *d_triple, Segments a, Segments b,
+                       Grid grid, Launch launch, const Planes &planes = Planes())
+{
+    const int pairs = call_pairs(a, b, grid);
+    Tail t = make_tail(c, pairs, scale1, scale2, n, d_triple, planes.count, planes.stride);
+    if (planes.pairs)
+        t.partials = planes.pairs;
+    t.total *= (uint32_t)planes.grid_y;   // arrivals of the whole call (0 in the two-launch form)
+    int slot = 0, which = 0;
+    uint64_t done = 0;
+    for (const Segments &list : {a, b}) {
+        for (const Segment &s : list) {
+            const int g = grid(s, which);
+            t.slot_base = (uint32_t)slot;
+            t.ticket_base = (uint32_t)(slot * planes.grid_y);
+            if (int rc = launch(t, s, g, done, which)) return rc;
+            slot += g;
+            done += s.count;
+        }
+        ++which;
+    }
+    return finish_call(c, t, pairs, st);
+}
+
+// ---- behind the wait of a synchronous call (run_sync, planes_run, the book's run form) ----
+using host_clock = std::chrono::steady_clock;
+static double ms_between(host_clock::time_point a, host_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// Whatever way out of a synchronous call: the stage accumulators and flags belong to ONE call
+struct CallStatsScope {
+    mc_context *c;
+    ~CallStatsScope() { c->acc_setup_ms = c->acc_table_ms = 0, c->stats_timed_call = false; }
+};
+
+// Closes the triple h = {sum, sum2, n} that a call of n paths brought back into *r.  n <= 2^52 (check_common), so the n word compares
+// exactly.  book_entry >= 0: the triple is that entry's of a vanilla book, and the error says so.
+static int close_triple(const double *h, uint64_t n, double discount, float kernel_ms, mc_result *r, int book_entry = -1)
+{
+    if (!(h[2] == (double)n)) {   // also catches the poison (NaN) of a reduction that never closed
+        if (book_entry >= 0)
+            return fail(MC_ERR_HIP, "vanilla book: entry %d: device returned n=%g, expected %llu: its final reduction did not complete", book_entry,
+                        h[2], (unsigned long long)n);
+        return fail(MC_ERR_HIP, "device returned n=%g, expected %llu: the call's final reduction did not complete", h[2], (unsigned long long)n);
+    }
+    r->sum = h[0], r->sum2 = h[1], r->n = n, r->kernel_ms = kernel_ms;
+    mc_closing(r->sum, r->sum2, r->n, discount, &r->expected, &r->confidence);
+    return MC_OK;
+}
+
+// The stage breakdown of a synchronous call (mc_context_last_call_stats): consecutive host-clock intervals between its start, the end of
+// its enqueue, the arrival of the result and the end of the closing; the device's kernel time is taken out of the wait
+static void record_call_stats(mc_context *c, host_clock::time_point wall0, host_clock::time_point t_enqueued, host_clock::time_point t_result,
+                              host_clock::time_point t_closed, float kernel_ms)
+{
+    mc_call_stats &k = c->stats;
+    const double before = ms_between(wall0, t_enqueued), wait = ms_between(t_enqueued, t_result);
+    k.setup_ms = (float)c->acc_setup_ms;
+    k.table_upload_ms = (float)c->acc_table_ms;
+    k.launch_ms = (float)std::max(0.0, before - c->acc_setup_ms - c->acc_table_ms);
+    // the events' figure, capped at the host's wait: the opening event is stamped when the idle device reaches it, so on the FIRST launch
+    // of a kernel it also spans the code-object load the host spent inside the launch call (already counted in launch_ms)
+    k.kernel_ms = (float)std::min((double)kernel_ms, wait);
+    k.readback_ms = (float)std::max(0.0, wait - (double)k.kernel_ms);
+    k.closing_ms = (float)ms_between(t_result, t_closed);
+    k.wall_ms = (float)ms_between(wall0, t_closed);
+    k.context_create_ms = c->create_ms;
+    k.first_call = c->sync_calls++ == 0;
+}
+
 // ---------------------------------------------------------------------------------------
 // XORWOW: jump matrices and per-lane start states (device side: mc_rng.hpp)
 // ---------------------------------------------------------------------------------------
@@ -876,36 +1018,16 @@ static int ensure_out(mc_context *c, size_t bytes)
 
 static constexpr uint64_t MAX_DUMP_PATHS = 1ull << 26;
 
-// The context's one per-call constant table (CVA per-date rows, or a generic basket's folded
-// constants): rebuilt and re-uploaded only when the inputs (the key) change.
-static int upload_table(mc_context *c, hipStream_t st, const std::vector<char> &key, const void *data, size_t bytes)
+// The content key of a table of Reals (mc_context::table): its bytes, the precision, and a letter for the kind of table
+template <class Real>
+static std::vector<char> table_key(const std::vector<Real> &host, char kind)
 {
-    if (key != c->table_key) {
-        StageTimer stage(&c->acc_table_ms);
-        if (bytes > c->table_bytes) {
-            HIPCHK(hipStreamSynchronize(st));
-            if (c->table_stream && c->table_stream != st) HIPCHK(hipStreamSynchronize(c->table_stream));
-            if (int rc = quiesce(c)) return rc;   // a launch on another caller stream may still read the old table
-            if (c->d_table) HIPCHK(hipFree(c->d_table));
-            if (c->h_table) HIPCHK(hipHostFree(c->h_table));
-            c->table_bytes = bytes < 4096 ? 4096 : bytes;
-            HIPCHK(hipMalloc(&c->d_table, c->table_bytes));
-            HIPCHK(hipHostMalloc(&c->h_table, c->table_bytes, hipHostMallocDefault));
-        } else {
-            HIPCHK(hipEventSynchronize(c->table_copied));  // previous upload has left the staging buffer
-        }
-        if (bytes) {
-            memcpy(c->h_table, data, bytes);
-            HIPCHK(hipMemcpyAsync(c->d_table, c->h_table, bytes, hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(hipEventRecord(c->table_copied, st));
-        c->table_stream = st;
-        c->table_key = key;
-    } else if (st != c->table_stream) {
-        // cached table uploaded on another stream: order this stream behind that upload
-        HIPCHK(hipStreamWaitEvent(st, c->table_copied, 0));
-    }
-    return MC_OK;
+    const size_t bytes = host.size() * sizeof(Real);
+    std::vector<char> key(bytes + 2);
+    memcpy(key.data(), host.data(), bytes);
+    key[bytes] = (char)sizeof(Real);
+    key[bytes + 1] = kind;
+    return key;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -941,7 +1063,7 @@ template <> struct VanillaTraits<float> {
         const double a2 = drift * log2e, b2 = vol * log2e;
         // Box-Muller on 32-bit uniforms cannot exceed |z| = sqrt(2 * 33 ln 2) = 6.764 (u >= 2^-33);
         // k makes 2^(a2 - k + b2 z) - K/(S 2^k) <= 1 for all of them, so the device's [0,1] clamp is exact.
-        // A negative strike RAISES the payoff (S_T + |K|): it enters the bound like the basket's does (basket_launch_n).
+        // A negative strike RAISES the payoff (S_T + |K|): it enters the bound like the basket's does (basket_args).
         const double zmax = 6.77;
         const double k = std::ceil(std::log2(std::exp2(a2 + b2 * zmax) + ((double)o.k < 0 ? -(double)o.k / (double)o.s : 0.0)));
         if (!(std::fabs(k) < 100))
@@ -1052,32 +1174,23 @@ static int vanilla_enqueue(mc_context *c, const typename VanillaTraits<Real>::In
         return fail(MC_ERR_INVALID, "external normals: one segment starting at path 0");
     const int scale = (sizeof(Real) == 8 && !c->ext) ? GRID_SCALE_VANILLA_F64 : 2;
     const auto grid = [&](uint32_t units) { return out ? grid_for(c->blocks, units) : grid_for_vanilla(c->blocks, c->compute_units, units, scale); };
-    int total = (has_head ? 1 : 0) + (has_tail ? 1 : 0);
-    for (const Segment &s : segs)
-        total += grid(s.count);
-    Tail t = make_tail(c, total, scale1, scale2, n, d_triple);
-    int slot = 0;
-    for (const Segment &s : segs) {
-        const Work w = context_work(c, seed, s, first, end);
-        const int g = grid(s.count);
-        t.slot_base = t.ticket_base = (uint32_t)slot;
-        if (out) {
-            if (int rc = launch_vanilla_masked<Real>(c, anti, k, w, t, g, st, out, (Real)scale1)) return rc;
-        } else if (int rc = T::launch_hot(c, prof, anti, k, w, t, g, st))
-            return rc;
-        slot += g;
-    }
-    for (int e = 0; e < 2; ++e) {
-        if (!(e == 0 ? has_head : has_tail))
-            continue;
-        Work w = context_work(c, seed, Segment{e == 0 ? head : tail_unit, 1u}, first, end);
-        if (w.ext)   // the external array is indexed from the launch's first unit
-            w.ext = static_cast<const Real *>(w.ext) + w.unit_lo * (uint64_t)w.ext_per_unit;
-        t.slot_base = t.ticket_base = (uint32_t)slot;
-        if (int rc = launch_vanilla_masked<Real>(c, anti, k, w, t, 1, st, (Real *)nullptr, (Real)1)) return rc;
-        slot += 1;
-    }
-    return finish_call(c, t, total, st);
+    Segment edges[2];
+    size_t n_edges = 0;
+    if (has_head) edges[n_edges++] = {head, 1u};
+    if (has_tail) edges[n_edges++] = {tail_unit, 1u};
+    return launch_call(
+        c, st, scale1, scale2, n, d_triple, segs, Segments(edges, n_edges), [&](const Segment &s, int edge) { return edge ? 1 : grid(s.count); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t, int edge) -> int {
+            Work w = context_work(c, seed, s, first, end);
+            if (edge) {
+                if (w.ext)   // the external array is indexed from the launch's first unit
+                    w.ext = static_cast<const Real *>(w.ext) + w.unit_lo * (uint64_t)w.ext_per_unit;
+                return launch_vanilla_masked<Real>(c, anti, k, w, t, 1, st, (Real *)nullptr, (Real)1);
+            }
+            if (out)
+                return launch_vanilla_masked<Real>(c, anti, k, w, t, g, st, out, (Real)scale1);
+            return T::launch_hot(c, prof, anti, k, w, t, g, st);
+        });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1155,7 +1268,8 @@ static int book_prepare(mc_context *c, const typename BookIn<Real>::type *entrie
     return MC_OK;
 }
 
-// The book's buffers, at least this large; the ticket words of a new buffer start at zero.  Behind quiesce, as ensure_planes.
+// The book's buffers, at least this large; the ticket words of a new buffer start at zero.  Behind quiesce: a launch on another
+// caller stream may still use the old ones.
 static int book_buffers(mc_context *c, size_t chunks, size_t counter_words, size_t entries)
 {
     mc_context::Book &k = c->book;
@@ -1187,40 +1301,6 @@ static int book_buffers(mc_context *c, size_t chunks, size_t counter_words, size
     return MC_OK;
 }
 
-// The book's tables into HBM, unless the same bytes are already there (cached by content, in a slot of their own: alternating
-// with CVA or generic-basket calls re-uploads neither table).
-static int book_upload(mc_context *c, hipStream_t st, const std::vector<char> &tables)
-{
-    mc_context::Book &k = c->book;
-    if (tables == k.key) {
-        if (st != k.stream)   // uploaded on another stream: order this one behind that upload
-            HIPCHK(hipStreamWaitEvent(st, k.copied, 0));
-        return MC_OK;
-    }
-    StageTimer stage(&c->acc_table_ms);
-    if (tables.size() > k.table_bytes) {
-        HIPCHK(hipStreamSynchronize(st));
-        if (k.stream && k.stream != st) HIPCHK(hipStreamSynchronize(k.stream));
-        if (int rc = quiesce(c)) return rc;   // a launch on another caller stream may still read the old tables
-        if (k.d_tables) HIPCHK(hipFree(k.d_tables));
-        if (k.h_tables) HIPCHK(hipHostFree(k.h_tables));
-        k.d_tables = k.h_tables = nullptr, k.table_bytes = 0, k.key.clear();
-        const size_t n = std::max(tables.size() + tables.size() / 4, (size_t)65536);
-        HIPCHK(hipMalloc(&k.d_tables, n));
-        HIPCHK(hipHostMalloc(&k.h_tables, n, hipHostMallocDefault));
-        k.table_bytes = n;
-    } else {
-        HIPCHK(hipEventSynchronize(k.copied));   // the previous upload has left the staging buffer
-    }
-    k.key.clear();   // until the copy below is enqueued, the device bytes are no longer what the key says
-    memcpy(k.h_tables, tables.data(), tables.size());
-    HIPCHK(hipMemcpyAsync(k.d_tables, k.h_tables, tables.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(k.copied, st));
-    k.stream = st;
-    k.key = tables;
-    return MC_OK;
-}
-
 // Persistent grid: at most `blocks` (fp64: GRID_SCALE_VANILLA_F64 / 2 x blocks) workgroups, as few as give every workgroup the same
 // number of chunks, give or take one.
 static int book_grid(const mc_context *c, size_t chunks, size_t real_bytes)
@@ -1236,9 +1316,10 @@ static int book_enqueue(mc_context *c, const BookPrepared &b, double *d_triples,
 {
     const size_t nch = b.plan.chunks.size();
     if (int rc = book_buffers(c, nch, b.plan.counter_words, (size_t)b.count)) return rc;
-    if (int rc = book_upload(c, st, b.tables)) return rc;
+    // cached by content, in a table of their own: alternating with CVA or generic-basket calls re-uploads neither table
     mc_context::Book &k = c->book;
-    const char *base = static_cast<const char *>(k.d_tables);
+    if (int rc = k.tables.upload(c, st, b.tables, b.tables.data(), b.tables.size())) return rc;
+    const char *base = static_cast<const char *>(k.tables.d);
     const BookChunk *chunks = reinterpret_cast<const BookChunk *>(base);
     const BookHead *heads = reinterpret_cast<const BookHead *>(base + b.heads_at);
     using Opt = typename VanillaTraits<Real>::Opt;
@@ -1281,18 +1362,13 @@ static int book_launch(mc_context *c, const typename BookIn<Real>::type *entries
 template <class Real>
 static int book_run(mc_context *c, const typename BookIn<Real>::type *entries, int count, mc_result *out)
 {
-    using clock = std::chrono::steady_clock;
-    const auto ms_between = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto wall0 = clock::now();
+    const auto wall0 = host_clock::now();
     BookPrepared b;
     if (int rc = book_prepare<Real>(c, entries, count, b)) return rc;
     if (!out) return fail(MC_ERR_INVALID, "NULL output pointer");
     c->acc_setup_ms = c->acc_table_ms = 0, c->call_t0_valid = false;
-    c->armed = false;   // as run_sync: a synchronous call cancels mc_context_arm_direct
-    struct Scope {
-        mc_context *c;
-        ~Scope() { c->acc_setup_ms = c->acc_table_ms = 0; }
-    } scope{c};
+    c->armed = false;   // a synchronous call cancels mc_context_arm_direct
+    CallStatsScope scope{c};
     const hipStream_t st = c->stream;
     if (int rc = begin_call(c, st)) return rc;
     {
@@ -1302,42 +1378,26 @@ static int book_run(mc_context *c, const typename BookIn<Real>::type *entries, i
     double *d_triples = c->book.d_triples;
     // poison (all bits set: NaN): an entry that never closes must not hand back the previous call's triple
     HIPCHK(hipMemsetAsync(d_triples, 0xFF, 3 * sizeof(double) * (size_t)count, st));
-    if (int rc = book_upload(c, st, b.tables)) return rc;
+    if (int rc = c->book.tables.upload(c, st, b.tables, b.tables.data(), b.tables.size())) return rc;
     if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));   // timing off (mc_context_set_timing): kernel_ms is reported as 0
     if (int rc = book_enqueue<Real>(c, b, d_triples, st)) return rc;
     if (c->timing) HIPCHK(hipEventRecord(c->ev1, st));
-    const auto t_enqueued = clock::now();
+    const auto t_enqueued = host_clock::now();
     std::vector<double> h(3 * (size_t)count);
     HIPCHK(hipMemcpyAsync(h.data(), d_triples, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const auto t_result = clock::now();
+    const auto t_result = host_clock::now();
     float ms = 0;
     if (c->timing) HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     for (int i = 0; i < count; ++i) {
-        const uint64_t n = entries[i].n_paths;
-        if (!(h[3 * i + 2] == (double)n))   // also catches the poison of an entry that never closed
-            return fail(MC_ERR_HIP, "vanilla book: entry %d: device returned n=%g, expected %llu: its final reduction did not complete", i,
-                        h[3 * i + 2], (unsigned long long)n);
-        mc_result &r = out[i];
-        r.sum = h[3 * i], r.sum2 = h[3 * i + 1], r.n = n, r.kernel_ms = ms;
         const double disc = std::exp(-(double)entries[i].option.r * (double)entries[i].option.t);
-        mc_closing(r.sum, r.sum2, r.n, disc, &r.expected, &r.confidence);
+        if (int rc = close_triple(&h[3 * (size_t)i], entries[i].n_paths, disc, ms, &out[i], i)) return rc;
     }
-    const auto t_closed = clock::now();
+    const auto t_closed = host_clock::now();
     const float wall = (float)ms_between(wall0, t_closed);
     for (int i = 0; i < count; ++i)
         out[i].wall_ms = wall;
-    mc_call_stats &k = c->stats;   // the stage breakdown of the book call (mc_context_last_call_stats), as run_sync
-    const double before = ms_between(wall0, t_enqueued), wait = ms_between(t_enqueued, t_result);
-    k.setup_ms = (float)c->acc_setup_ms;
-    k.table_upload_ms = (float)c->acc_table_ms;
-    k.launch_ms = (float)std::max(0.0, before - c->acc_setup_ms - c->acc_table_ms);
-    k.kernel_ms = (float)std::min((double)ms, wait);
-    k.readback_ms = (float)std::max(0.0, wait - (double)k.kernel_ms);
-    k.closing_ms = (float)ms_between(t_result, t_closed);
-    k.wall_ms = wall;
-    k.context_create_ms = c->create_ms;
-    k.first_call = c->sync_calls++ == 0;
+    record_call_stats(c, wall0, t_enqueued, t_result, t_closed, ms);
     return MC_OK;
 }
 
@@ -1406,7 +1466,7 @@ template <class Launch>
 static int planes_run(mc_context *c, size_t real_bytes, int planes, int grid_y, uint64_t unit0, uint64_t n_units, uint64_t n, double discount,
                       mc_result **out, Launch launch)
 {
-    const auto wall0 = std::chrono::steady_clock::now();
+    const auto wall0 = host_clock::now();
     hipStream_t st = c->stream;
     if (c->rng != MC_RNG_PHILOX || (real_bytes == 8 && c->normals_f32))
         return fail(MC_ERR_UNSUPPORTED, "greeks: implemented for the Philox generator with native normals only");
@@ -1418,40 +1478,29 @@ static int planes_run(mc_context *c, size_t real_bytes, int planes, int grid_y, 
         return fail(MC_ERR_INVALID, "greeks: path range too large for one call; split it");
     HIPCHK(hipMemsetAsync(c->g_triples, 0xFF, sizeof(double) * 3 * (size_t)planes, st));   // poison: see run_sync
     HIPCHK(hipEventRecord(c->ev0, st));
-    int pairs = 0;
-    for (const Segment &s : segs)
-        pairs += grid_for(c->blocks, s.count);
+    const auto grid = [&](const Segment &s, int) { return grid_for(c->blocks, s.count); };
+    const int pairs = call_pairs(segs, {}, grid);
     if ((uint64_t)pairs * (uint64_t)grid_y > UINT32_MAX)   // the tickets of the call's arrivals are 32-bit
         return fail(MC_ERR_INVALID, "greeks: %d workgroups x %d passes do not fit in one call; use fewer blocks", pairs, grid_y);
-    Tail t = make_tail(c, pairs, 1.0, 1.0, n, c->g_triples, planes, 2 * c->blocks + 2);
-    t.partials = c->g_pairs;
-    if (c->fused)
-        t.total = (uint32_t)(pairs * grid_y);
-    int slot = 0;
-    for (const Segment &s : segs) {
-        const int g = grid_for(c->blocks, s.count);
-        t.slot_base = (uint32_t)slot;
-        t.ticket_base = (uint32_t)(slot * grid_y);
-        launch(t, s, g, st);
-        slot += g;
-    }
-    if (int rc = finish_call(c, t, pairs, st)) return rc;
+    const Planes where = {c->g_pairs, planes, 2 * c->blocks + 2, grid_y};
+    if (int rc = launch_call(
+            c, st, 1.0, 1.0, n, c->g_triples, segs, {}, grid,
+            [&](const Tail &t, const Segment &s, int g, uint64_t, int) {
+                launch(t, s, g, st);
+                return MC_OK;
+            },
+            where))
+        return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     std::vector<double> h(3 * (size_t)planes);
     HIPCHK(hipMemcpyAsync(h.data(), c->g_triples, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    const float wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    const float wall = std::chrono::duration<float, std::milli>(host_clock::now() - wall0).count();
     for (int q = 0; q < planes; ++q) {
-        mc_result *r = out[q];
-        if (!(h[3 * q + 2] == (double)n))
-            return fail(MC_ERR_HIP, "device returned n=%g, expected %llu: the call's final reduction did not complete", h[3 * q + 2],
-                        (unsigned long long)n);
-        r->sum = h[3 * q], r->sum2 = h[3 * q + 1], r->n = (uint64_t)h[3 * q + 2], r->kernel_ms = ms, r->wall_ms = wall;
-        if (r->n != n)
-            return fail(MC_ERR_HIP, "device returned n=%llu, expected %llu", (unsigned long long)r->n, (unsigned long long)n);
-        mc_closing(r->sum, r->sum2, r->n, discount, &r->expected, &r->confidence);
+        if (int rc = close_triple(&h[3 * (size_t)q], n, discount, ms, out[q])) return rc;
+        out[q]->wall_ms = wall;
     }
     return MC_OK;
 }
@@ -1578,48 +1627,97 @@ static int basket_launch_kernel(mc_context *c, ProfileScope &prof, bool anti, co
 // only be met on that model.  The drift keeps the true volatility, as it does there.
 static double diffusion_vol(const mc_context *c, double v) { return (c->ext && (c->ext_flags & MC_FROM_NORMALS_NO_VOL)) ? 1.0 : v; }
 
-// Folds a basket of o.n <= NA assets into the kernel-argument constants of size NA (rows beyond o.n: zero factor, base and
-// weight -- they add exactly 0 to the basket).  out_scale = what the kernel's per-path values are multiplied by to give
-// currency units (fp32: the exact power of two of the [0,1] rescale; 1/2 of it under antithetic variates, whose fp32
-// kernels return the SUM of the two mirrored payoffs).
-template <class Real, int NA>
-static int basket_fold(mc_context *c, const typename BasketIn<Real>::type &o, BasketArgs<Real, NA> &k, double &out_scale)
+// What every basket entry point checks of its inputs behind the size: the arrays and the scalars
+template <class In>
+static int basket_check_inputs(const In *o)
+{
+    if (!o->s || !o->v || !o->p || !o->d || !o->w)
+        return fail(MC_ERR_INVALID, "basket: NULL array");
+    if (!(o->t >= 0) || !std::isfinite((double)o->r) || !std::isfinite((double)o->k))
+        return fail(MC_ERR_INVALID, "basket: need t>=0 and finite r, k");
+    return MC_OK;
+}
+template <class In>
+static int basket_check(const In *o)
+{
+    if (o->n < 1 || o->n > MC_MAX_ASSETS_GENERIC)
+        return fail(MC_ERR_UNSUPPORTED, "basket: n=%d outside the supported range 1..%d", o->n, MC_MAX_ASSETS_GENERIC);
+    return basket_check_inputs(o);
+}
+
+// A basket of o.n <= CAP assets folded into the constants of its pricing kernels, in fp64 (sc = exp_scale<Real>(): the kernels' exponent
+// units): m[a][b] = vd sqrt(t) p[a][b] sc, base[a], coef[a] = w[a] s[a]; rows beyond o.n are zero -- they add exactly 0 to the basket.
+// Under the control variate also wg[a] = w[a] / W and cg = ln G in exponent units (basket_fold_control).  The callers only lay
+// these out, each rounding once to Real.
+template <int CAP>
+struct BasketFold {
+    double m[CAP][CAP], base[CAP], coef[CAP], wg[CAP], cg;
+};
+
+// guard_rounded_base: the exponent-range guard takes |base[a]| after rounding to Real (the tiled form's table entry) instead of before
+// (the kernel-argument form).  One number in fp64; in fp32 each form keeps the guard it has always had.
+template <class Real, int CAP>
+static int basket_fold(mc_context *c, const typename BasketIn<Real>::type &o, bool guard_rounded_base, BasketFold<CAP> &f)
 {
     const int n = o.n;
-    double scale = 1.0;
-    constexpr bool is_f32 = sizeof(Real) == 4;
     const double sc = exp_scale<Real>();
     const double sqrt_t = std::sqrt((double)o.t);
-    double m[NA][NA], base[NA], coef[NA];
-    for (int a = 0; a < NA; ++a) {
-        base[a] = coef[a] = 0;
-        for (int b = 0; b < NA; ++b)
-            m[a][b] = 0;
-    }
+    f = {};
     for (int a = 0; a < n; ++a) {
         const double va = (double)o.v[a];
         const double vd = diffusion_vol(c, va);   // va, except under the bridge tests' reference-CPU-bug switch
         for (int b = 0; b <= a; ++b)
-            m[a][b] = vd * sqrt_t * (double)o.p[a * n + b] * sc;
-        base[a] = (((double)o.r - 0.5 * va * va) * (double)o.t + vd * sqrt_t * (double)o.d[a]) * sc;
-        coef[a] = (double)o.w[a] * (double)o.s[a];
-        double bound = std::fabs(base[a]);
+            f.m[a][b] = vd * sqrt_t * (double)o.p[a * n + b] * sc;
+        f.base[a] = (((double)o.r - 0.5 * va * va) * (double)o.t + vd * sqrt_t * (double)o.d[a]) * sc;
+        f.coef[a] = (double)o.w[a] * (double)o.s[a];
+        double bound = std::fabs(guard_rounded_base ? (double)(Real)f.base[a] : f.base[a]);
         for (int b = 0; b <= a; ++b)
-            bound += std::fabs(m[a][b]) * Z_MAX_F64;
+            bound += std::fabs(f.m[a][b]) * Z_MAX_F64;
         if (!exponent_in_range(bound / sc))
             return fail(MC_ERR_INVALID, "basket: asset %d's drift and volatility put its terminal price outside the range of a double", a);
     }
-    scale = 1.0;
+    return MC_OK;
+}
+
+// the control variate's part of the fold, when the context has it on (f.wg and f.cg stay zero otherwise)
+template <class Real, int CAP>
+static int basket_fold_control(mc_context *c, const typename BasketIn<Real>::type &o, BasketFold<CAP> &f)
+{
+    if (!c->control)
+        return MC_OK;
+    double cv_mean;
+    if (int rc = control_mean(o, &cv_mean)) return rc;  // validates w > 0, s > 0, k > 0
+    double W = 0, cg = 0;
+    for (int a = 0; a < o.n; ++a)
+        W += (double)o.w[a];
+    for (int a = 0; a < o.n; ++a) {
+        f.wg[a] = (double)o.w[a] / W;
+        cg += (double)o.w[a] / W * std::log((double)o.s[a]);
+    }
+    f.cg = (cg + std::log(W)) * exp_scale<Real>();
+    return MC_OK;
+}
+
+// The kernel-argument form of the fold: packed rows of size NA.  out_scale = what the kernel's per-path values are multiplied by to give
+// currency units (fp32: the exact power of two of the [0,1] rescale; 1/2 of it under antithetic variates, whose fp32
+// kernels return the SUM of the two mirrored payoffs).
+template <class Real, int NA>
+static int basket_args(mc_context *c, const typename BasketIn<Real>::type &o, BasketArgs<Real, NA> &k, double &out_scale)
+{
+    constexpr bool is_f32 = sizeof(Real) == 4;
+    BasketFold<NA> f;
+    if (int rc = basket_fold<Real>(c, o, false, f)) return rc;
+    double scale = 1.0;
     if (is_f32) {
         // |z| < 6.77 for every normal the f32 generator can produce: bound the basket and rescale by
         // an exact power of two so that the device's [0,1] clamp is the payoff's max(.,0)
         const double zmax = 6.77;
         double bound = 0;
-        for (int a = 0; a < n; ++a) {
-            double x = base[a];
+        for (int a = 0; a < o.n; ++a) {
+            double x = f.base[a];
             for (int b = 0; b <= a; ++b)
-                x += std::fabs(m[a][b]) * zmax;
-            bound += std::fabs(coef[a]) * std::exp2(x);
+                x += std::fabs(f.m[a][b]) * zmax;
+            bound += std::fabs(f.coef[a]) * std::exp2(x);
         }
         // a negative strike RAISES the payoff: basket - K <= bound + |K| must still fit the [0,1] clamp
         if ((double)o.k < 0)
@@ -1630,30 +1728,18 @@ static int basket_fold(mc_context *c, const typename BasketIn<Real>::type &o, Ba
         scale = std::ldexp(1.0, (int)kk);
     }
     out_scale = (is_f32 && c->antithetic) ? 0.5 * scale : scale;  // f32 anti: kernel returns the SUM
+    if (int rc = basket_fold_control<Real>(c, o, f)) return rc;
     for (int a = 0; a < NA; ++a) {
         for (int b = 0; b <= a; ++b)
-            k.m[a * (a + 1) / 2 + b] = (Real)m[a][b];
-        k.base[a] = (Real)base[a];
-        k.coef[a] = (Real)(coef[a] / scale);
-        k.wg[a] = 0;
+            k.m[a * (a + 1) / 2 + b] = (Real)f.m[a][b];
+        k.base[a] = (Real)f.base[a];
+        k.coef[a] = (Real)(f.coef[a] / scale);
+        k.wg[a] = (Real)f.wg[a];
     }
     k.strike = (Real)((double)o.k / scale);
-    k.cg = 0;
-    k.cv = 0;
-    if (c->control) {
-        double cv_mean;
-        if (int rc = control_mean(o, &cv_mean)) return rc;  // validates w > 0, s > 0, k > 0
-        double W = 0, cg = 0;
-        for (int a = 0; a < n; ++a)
-            W += (double)o.w[a];
-        for (int a = 0; a < n; ++a) {
-            k.wg[a] = (Real)((double)o.w[a] / W);
-            cg += (double)o.w[a] / W * std::log((double)o.s[a]);
-        }
-        // ln G in the kernel's exponent units (log2 in f32), minus the power-of-two rescale
-        k.cg = (Real)((cg + std::log(W)) * sc - (is_f32 ? std::log2(scale) : 0.0));
-        k.cv = 1;
-    }
+    // ln G in the kernel's exponent units (log2 in f32), minus the power-of-two rescale
+    k.cg = c->control ? (Real)(f.cg - (is_f32 ? std::log2(scale) : 0.0)) : (Real)0;
+    k.cv = c->control ? 1 : 0;
     return MC_OK;
 }
 
@@ -1664,91 +1750,65 @@ static int basket_launch_n(mc_context *c, ProfileScope &prof, const typename Bas
     constexpr bool is_f32 = sizeof(Real) == 4;
     BasketArgs<Real, NA> k;
     double out_scale = 1.0;
-    if (int rc = basket_fold<Real, NA>(c, o, k, out_scale)) return rc;
-    int total = 0, slot = 0;
-    for (const Segment &s : segs)
-        total += grid_for(c->blocks, is_f32 ? (s.count + 1) / 2 : s.count);
-    Tail t = make_tail(c, total, out_scale, out_scale * out_scale, n_paths, d_triple);
-    uint64_t done = 0;
-    for (const Segment &s : segs) {
-        const Work w = context_work(c, seed, s, 0, 0);
-        const int g = grid_for(c->blocks, is_f32 ? (s.count + 1) / 2 : s.count);
-        t.slot_base = t.ticket_base = (uint32_t)slot;
-        if (int rc = basket_launch_kernel<NA>(c, prof, c->antithetic, k, w, t, out ? out + done : (Real *)nullptr, out_scale, g, st))
-            return rc;
-        slot += g;
-        done += s.count;
-    }
-    return finish_call(c, t, total, st);
+    if (int rc = basket_args<Real, NA>(c, o, k, out_scale)) return rc;
+    return launch_call(
+        c, st, out_scale, out_scale * out_scale, n_paths, d_triple, segs, {},
+        [&](const Segment &s, int) { return grid_for(c->blocks, is_f32 ? (s.count + 1) / 2 : s.count); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            return basket_launch_kernel<NA>(c, prof, c->antithetic, k, context_work(c, seed, s, 0, 0), t, out ? out + done : (Real *)nullptr,
+                                            out_scale, g, st);
+        });
 }
 
-// The table-driven families: fold the constants exactly like basket_launch_n (no power-of-two rescale:
-// these kernels take the plain max), lay them out in 4 x 4 tiles, park them in the context's table
-// buffer and run the tiled kernel of the size, or the generic one beyond 32 assets.
+// The table form of the fold (no power-of-two rescale: these kernels take the plain max): BasketDyn::consts = 4 x 4 tiles of the
+// lower-triangular matrix, block-row by block-row (tile (A, c4) = 16 reals, index 4 j + r = m[4A + r][4 c4 + j], zero outside
+// the triangle / beyond n), then base, coef, wg padded with zeros to 4 nb entries; fp64 with 13..16 assets: the same matrix once more
+// as the A operands of the matrix-core kernel (basket_mfma_f64_kernel: a4[s][lane] = M[lane & 15][k(s, lane >> 4)],
+// k(s, q) = 2 q + (s & 1) + 8 (s >> 1)).  *cg = BasketDyn::cg.
 template <class Real>
-static int basket_launch_dyn(mc_context *c, ProfileScope &prof, const typename BasketIn<Real>::type &o, uint64_t seed,
-                             const std::vector<Segment> &segs, hipStream_t st, Real *out, uint64_t n_paths, double *d_triple)
+static int basket_table(mc_context *c, const typename BasketIn<Real>::type &o, std::vector<Real> &host, Real *cg)
 {
-    // layout of BasketDyn::consts: 4 x 4 tiles of the folded lower-triangular matrix, block-row by block-row
-    // (tile (A, c4) = 16 reals, index 4 j + r = m[4A + r][4 c4 + j], zero outside the triangle / beyond n),
-    // then base, coef, wg padded with zeros to 4 nb entries
+    BasketFold<MC_MAX_ASSETS_GENERIC> f;
+    if (int rc = basket_fold<Real>(c, o, true, f)) return rc;
+    if (int rc = basket_fold_control<Real>(c, o, f)) return rc;
     const int n = o.n, nb = (n + 3) / 4, np = 4 * nb;
     const size_t n_tiles = (size_t)8 * nb * (nb + 1);
-    const double sc = exp_scale<Real>();
-    const double sqrt_t = std::sqrt((double)o.t);
-    // fp64, 13..16 assets: the same matrix once more as the A operands of the matrix-core kernel (basket_mfma_f64_kernel:
-    // a4[s][lane] = M[lane & 15][k(s, lane >> 4)], k(s, q) = 2 q + (s & 1) + 8 (s >> 1))
     const bool with_a4 = sizeof(Real) == 8 && np == 16;
-    std::vector<Real> host(n_tiles + 3 * (size_t)np + (with_a4 ? 256 : 0), (Real)0);
-    if (with_a4)
-        for (int s4 = 0; s4 < 4; ++s4)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int a = lane & 15, b = 2 * (lane >> 4) + (s4 & 1) + 8 * (s4 >> 1);
-                if (a < n && b <= a)
-                    host[n_tiles + 3 * (size_t)np + 64 * s4 + lane] = (Real)(diffusion_vol(c, (double)o.v[a]) * sqrt_t * (double)o.p[a * n + b] * sc);
-            }
+    host.assign(n_tiles + 3 * (size_t)np + (with_a4 ? 256 : 0), (Real)0);
     size_t t = 0;
     for (int A = 0; A < nb; ++A)
         for (int c4 = 0; c4 <= A; ++c4, t += 16)
             for (int j = 0; j < 4; ++j)
-                for (int r = 0; r < 4; ++r) {
-                    const int a = 4 * A + r, b = 4 * c4 + j;
-                    if (a < n && b <= a)
-                        host[t + 4 * j + r] = (Real)(diffusion_vol(c, (double)o.v[a]) * sqrt_t * (double)o.p[a * n + b] * sc);
-                }
+                for (int r = 0; r < 4; ++r)   // (rows beyond n and entries above the diagonal are zero in f.m)
+                    host[t + 4 * j + r] = (Real)f.m[4 * A + r][4 * c4 + j];
     for (int a = 0; a < n; ++a) {
-        const double va = (double)o.v[a], vd = diffusion_vol(c, va);
-        host[n_tiles + a] = (Real)((((double)o.r - 0.5 * va * va) * (double)o.t + vd * sqrt_t * (double)o.d[a]) * sc);
-        host[n_tiles + np + a] = (Real)((double)o.w[a] * (double)o.s[a]);
-        double bound = std::fabs((double)host[n_tiles + a]);
-        for (int b = 0; b <= a; ++b)
-            bound += std::fabs(vd * sqrt_t * (double)o.p[a * n + b] * sc) * Z_MAX_F64;
-        if (!exponent_in_range(bound / sc))
-            return fail(MC_ERR_INVALID, "basket: asset %d's drift and volatility put its terminal price outside the range of a double", a);
+        host[n_tiles + a] = (Real)f.base[a];
+        host[n_tiles + np + a] = (Real)f.coef[a];
+        host[n_tiles + 2 * np + a] = (Real)f.wg[a];
     }
-    double cg_dyn = 0;
-    if (c->control) {
-        double cv_mean, W = 0;
-        if (int rc = control_mean(o, &cv_mean)) return rc;
-        for (int a = 0; a < n; ++a)
-            W += (double)o.w[a];
-        for (int a = 0; a < n; ++a) {
-            host[n_tiles + 2 * np + a] = (Real)((double)o.w[a] / W);
-            cg_dyn += (double)o.w[a] / W * std::log((double)o.s[a]);
-        }
-        cg_dyn = (cg_dyn + std::log(W)) * sc;
-    }
-    const size_t bytes = host.size() * sizeof(Real);
-    std::vector<char> key(bytes + 2);
-    memcpy(key.data(), host.data(), bytes);
-    key[bytes] = (char)sizeof(Real);
-    key[bytes + 1] = 'B';
-    if (int rc = upload_table(c, st, key, host.data(), bytes)) return rc;
+    if (with_a4)
+        for (int s4 = 0; s4 < 4; ++s4)
+            for (int lane = 0; lane < 64; ++lane)
+                host[n_tiles + 3 * (size_t)np + 64 * s4 + lane] = (Real)f.m[lane & 15][2 * (lane >> 4) + (s4 & 1) + 8 * (s4 >> 1)];
+    *cg = (Real)f.cg;
+    return MC_OK;
+}
+
+// The table-driven families: the folded constants parked in the context's table buffer, and the tiled kernel of the size or the
+// generic one beyond 32 assets.
+template <class Real>
+static int basket_launch_dyn(mc_context *c, ProfileScope &prof, const typename BasketIn<Real>::type &o, uint64_t seed,
+                             const std::vector<Segment> &segs, hipStream_t st, Real *out, uint64_t n_paths, double *d_triple)
+{
+    const int n = o.n, np = (n + 3) / 4 * 4;
+    const bool with_a4 = sizeof(Real) == 8 && np == 16;
+    std::vector<Real> host;
     BasketDyn<Real> k;
-    k.consts = (const Real *)c->d_table;
+    if (int rc = basket_table<Real>(c, o, host, &k.cg)) return rc;
+    if (int rc = c->table.upload(c, st, table_key(host, 'B'), host.data(), host.size() * sizeof(Real))) return rc;
+    k.consts = (const Real *)c->table.d;
     k.n = n;
     k.strike = o.k;
-    k.cg = (Real)cg_dyn;
     k.cv = c->control ? 1 : 0;
     // Pick the kernel.  `gen` = the generator policy of this call; families and what they are compiled for:
     //   generic one-path-per-lane (basket_dyn_kernel)      every generator, any n
@@ -1818,32 +1878,19 @@ static int basket_launch_dyn(mc_context *c, ProfileScope &prof, const typename B
         HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the tiled (register-resident) kernels launch more, smaller workgroups (grid_for); the generic ones keep 1x
     const int scale = (lds == 0 && tiled_ok && gen != GEN_XORWOW) ? (sizeof(Real) == 8 ? GRID_SCALE_TILED_F64 : GRID_SCALE_TILED_F32) : 2;
-    int total = 0, slot = 0;
-    for (const Segment &s : segs)
-        total += grid_for(c->blocks, pairs ? (s.count + 1) / 2 : s.count, scale);
-    Tail tail = make_tail(c, total, 1.0, 1.0, n_paths, d_triple);
-    uint64_t done = 0;
-    for (const Segment &s : segs) {
-        const Work w = context_work(c, seed, s, 0, 0);
-        const int g = grid_for(c->blocks, pairs ? (s.count + 1) / 2 : s.count, scale);
-        tail.slot_base = tail.ticket_base = (uint32_t)slot;
-        launch_sim_lds(prof, kernel, g, lds, st, tail, k, w, out ? out + done : (Real *)nullptr);
-        slot += g;
-        done += s.count;
-    }
-    return finish_call(c, tail, total, st);
+    return launch_call(
+        c, st, 1.0, 1.0, n_paths, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, pairs ? (s.count + 1) / 2 : s.count, scale); },
+        [&](const Tail &tail, const Segment &s, int g, uint64_t done, int) {
+            launch_sim_lds(prof, kernel, g, lds, st, tail, k, context_work(c, seed, s, 0, 0), out ? out + done : (Real *)nullptr);
+            return MC_OK;
+        });
 }
 
 template <class Real>
 static int basket_enqueue(mc_context *c, const typename BasketIn<Real>::type *o, uint64_t seed, uint64_t first,
                           uint64_t n, double *d_triple, hipStream_t st, Real *out)
 {
-    if (o->n < 1 || o->n > MC_MAX_ASSETS_GENERIC)
-        return fail(MC_ERR_UNSUPPORTED, "basket: n=%d outside the supported range 1..%d", o->n, MC_MAX_ASSETS_GENERIC);
-    if (!o->s || !o->v || !o->p || !o->d || !o->w)
-        return fail(MC_ERR_INVALID, "basket: NULL array");
-    if (!(o->t >= 0) || !std::isfinite((double)o->r) || !std::isfinite((double)o->k))
-        return fail(MC_ERR_INVALID, "basket: need t>=0 and finite r, k");
+    if (int rc = basket_check(o)) return rc;
     if (int rc = begin_call(c, st)) return rc;
     std::vector<Segment> segs;
     if (int rc = plan_segments(first, n, segs)) return rc;
@@ -1963,9 +2010,9 @@ static int cva_table_ready(mc_context *c, const typename CvaIn<Real>::type *v, h
                                  (double)v->n_grid, (double)sizeof(Real), (double)lag};
     std::vector<char> key(sizeof key_vals);
     memcpy(key.data(), key_vals, sizeof key_vals);
-    if (key == c->table_key && c->cva_args.size() == sizeof args) {   // same inputs as the table in HBM: nothing to rebuild
+    if (key == c->table.key && c->cva_args.size() == sizeof args) {   // same inputs as the table in HBM: nothing to rebuild
         memcpy(&args, c->cva_args.data(), sizeof args);
-        return upload_table(c, st, key, nullptr, 0);                  // (orders `st` behind the upload if it is another stream)
+        return c->table.upload(c, st, key, nullptr, 0);               // (orders `st` behind the upload if it is another stream)
     }
     static thread_local std::vector<CvaStep<Real>> tab;
     static thread_local std::vector<Real> extra, blob;
@@ -1986,13 +2033,13 @@ static int cva_table_ready(mc_context *c, const typename CvaIn<Real>::type *v, h
         }
     }
     memcpy(blob.data() + step_reals + pair_reals, extra.data(), extra.size() * sizeof(Real));
-    if (int rc = upload_table(c, st, key, blob.data(), blob.size() * sizeof(Real))) return rc;
+    if (int rc = c->table.upload(c, st, key, blob.data(), blob.size() * sizeof(Real))) return rc;
     args.pairs = nullptr;
     args.pairs_in_lds = 0;   // set per launch (cva_enqueue)
     if constexpr (sizeof(Real) == 4)
-        args.pairs = (const float *)c->d_table + step_reals;
-    args.extra = (const Real *)c->d_table + step_reals + pair_reals;
-    args.steps = (const CvaStep<Real> *)c->d_table;
+        args.pairs = (const float *)c->table.d + step_reals;
+    args.extra = (const Real *)c->table.d + step_reals + pair_reals;
+    args.steps = (const CvaStep<Real> *)c->table.d;
     c->cva_args.assign((const char *)&args, (const char *)&args + sizeof args);
     return MC_OK;
 }
@@ -2043,13 +2090,6 @@ static int cva_enqueue(mc_context *c, const typename CvaIn<Real>::type *v, uint6
             if (int rc = plan_segments(first, plan.tail_paths, tail_segs)) return rc;
     }
     const int scale = xorwow ? 2 : GRID_SCALE_CVA;
-    int total = 0, slot = 0;
-    for (const Segment &s : segs)
-        total += grid_for(c->blocks, s.count, scale);
-    for (const Segment &s : tail_segs)
-        total += grid_for_cva_dates(c->blocks, s.count, plan.log2_lanes);
-    Tail t = make_tail(c, total, 1.0, 1.0, n, d_triple);
-    uint64_t done = 0;
     ProfileScope prof(c);
     if (c->ext && (segs.size() + tail_segs.size() > 1 || first != 0))
         return fail(MC_ERR_INVALID, "external normals: one segment starting at path 0");
@@ -2063,48 +2103,41 @@ static int cva_enqueue(mc_context *c, const typename CvaIn<Real>::type *v, uint6
     // leaves the kernel its eight waves per SIMD (16 KB = 341 date pairs; a split launch already carries the whole table's LDS)
     const size_t pairs_lds = sizeof(Real) == 4 ? (size_t)48 * (size_t)(args.n_bs / 2) : 0;
     const bool pairs_fit = pairs_lds > 0 && pairs_lds <= 16 * 1024 && !c->antithetic;   // (the antithetic instantiation does not take them)
-    if (fused_split) {
+    if (fused_split) {   // ONE launch: the workgroups of the one-lane-per-path part, then those of the date-parallel part
         args.pairs_in_lds = pairs_lds > 0;
-        const Work w = context_work(c, seed, segs[0], 0, 0), wt = context_work(c, seed, tail_segs[0], 0, 0);
+        const Work wt = context_work(c, seed, tail_segs[0], 0, 0);
         const int g_tail = grid_for_cva_dates(c->blocks, tail_segs[0].count, plan.log2_lanes);
-        Real *dst = out, *dst_tail = out ? out + segs[0].count : (Real *)nullptr;
-        constexpr unsigned ALLOW = GEN_PHILOX | (sizeof(Real) == 8 ? GEN_F32N : 0);
-        if (int rc = with_gen<ALLOW>(gen_of(c, w, sizeof(Real)), [&](auto tag) {
-                launch_sim_lds(prof, cva_split_kernel<Real, CVA_DATES_CH, typename decltype(tag)::type>, total, table_lds, st, t, args, w, wt,
-                               (uint32_t)g_tail, (uint32_t)plan.log2_lanes, dst, dst_tail);
-            }))
-            return rc;
-        return finish_call(c, t, total, st);
+        Real *dst_tail = out ? out + segs[0].count : (Real *)nullptr;
+        return launch_call(
+            c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, scale) + g_tail; },
+            [&](const Tail &t, const Segment &s, int g, uint64_t, int) {
+                const Work w = context_work(c, seed, s, 0, 0);
+                constexpr unsigned ALLOW = GEN_PHILOX | (sizeof(Real) == 8 ? GEN_F32N : 0);
+                return with_gen<ALLOW>(gen_of(c, w, sizeof(Real)), [&](auto tag) {
+                    launch_sim_lds(prof, cva_split_kernel<Real, CVA_DATES_CH, typename decltype(tag)::type>, g, table_lds, st, t, args, w, wt,
+                                   (uint32_t)g_tail, (uint32_t)plan.log2_lanes, out, dst_tail);
+                });
+            });
     }
     args.pairs_in_lds = pairs_fit;
-    for (const Segment &s : segs) {
-        const Work w = context_work(c, seed, s, 0, 0);
-        const int g = grid_for(c->blocks, s.count, scale);
-        t.slot_base = t.ticket_base = (uint32_t)slot;
-        Real *dst = out ? out + done : (Real *)nullptr;
-        constexpr unsigned ALLOW = GEN_PHILOX | GEN_XORWOW | GEN_EXTERNAL | (sizeof(Real) == 8 ? GEN_F32N : 0);
-        if (int rc = with_anti_gen<ALLOW>(c->antithetic, gen_of(c, w, sizeof(Real)), [&](auto a, auto tag) {
-                launch_sim_lds(prof, cva_kernel<Real, decltype(a)::value, typename decltype(tag)::type>, g, pairs_fit ? pairs_lds : 0, st, t, args, w, dst);
-            }))
-            return rc;
-        slot += g;
-        done += s.count;
-    }
-    for (const Segment &s : tail_segs) {
-        const Work w = context_work(c, seed, s, 0, 0);
-        const int g = grid_for_cva_dates(c->blocks, s.count, plan.log2_lanes);
-        t.slot_base = t.ticket_base = (uint32_t)slot;
-        Real *dst = out ? out + done : (Real *)nullptr;
-        constexpr unsigned ALLOW = GEN_PHILOX | GEN_EXTERNAL | (sizeof(Real) == 8 ? GEN_F32N : 0);
-        if (int rc = with_anti_gen<ALLOW>(c->antithetic, gen_of(c, w, sizeof(Real)), [&](auto a, auto tag) {
-                launch_sim_lds(prof, cva_dates_kernel<Real, CVA_DATES_CH, decltype(a)::value, typename decltype(tag)::type>, g, table_lds, st, t,
-                               args, w, (uint32_t)plan.log2_lanes, dst);
-            }))
-            return rc;
-        slot += g;
-        done += s.count;
-    }
-    return finish_call(c, t, total, st);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, tail_segs,
+        [&](const Segment &s, int dates) { return dates ? grid_for_cva_dates(c->blocks, s.count, plan.log2_lanes) : grid_for(c->blocks, s.count, scale); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int dates) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (!dates) {
+                constexpr unsigned ALLOW = GEN_PHILOX | GEN_XORWOW | GEN_EXTERNAL | (sizeof(Real) == 8 ? GEN_F32N : 0);
+                return with_anti_gen<ALLOW>(c->antithetic, gen_of(c, w, sizeof(Real)), [&](auto a, auto tag) {
+                    launch_sim_lds(prof, cva_kernel<Real, decltype(a)::value, typename decltype(tag)::type>, g, pairs_fit ? pairs_lds : 0, st, t, args, w, dst);
+                });
+            }
+            constexpr unsigned ALLOW = GEN_PHILOX | GEN_EXTERNAL | (sizeof(Real) == 8 ? GEN_F32N : 0);
+            return with_anti_gen<ALLOW>(c->antithetic, gen_of(c, w, sizeof(Real)), [&](auto a, auto tag) {
+                launch_sim_lds(prof, cva_dates_kernel<Real, CVA_DATES_CH, decltype(a)::value, typename decltype(tag)::type>, g, table_lds, st, t, args, w,
+                               (uint32_t)plan.log2_lanes, dst);
+            });
+        });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2114,12 +2147,7 @@ static int cva_enqueue(mc_context *c, const typename CvaIn<Real>::type *v, uint6
 template <class Real, bool LR>
 static int basket_greeks_setup(mc_context *c, const typename BasketIn<Real>::type *o, BasketGreeks<Real> &k)
 {
-    if (o->n < 1 || o->n > MC_MAX_ASSETS_GENERIC)
-        return fail(MC_ERR_UNSUPPORTED, "basket: n=%d outside the supported range 1..%d", o->n, MC_MAX_ASSETS_GENERIC);
-    if (!o->s || !o->v || !o->p || !o->d || !o->w)
-        return fail(MC_ERR_INVALID, "basket: NULL array");
-    if (!(o->t >= 0) || !std::isfinite((double)o->r) || !std::isfinite((double)o->k))
-        return fail(MC_ERR_INVALID, "basket: need t>=0 and finite r, k");
+    if (int rc = basket_check(o)) return rc;
     if (int rc = greeks_plain_only(c->antithetic || c->control)) return rc;
     const int na = o->n;
     const double sqrt_t = std::sqrt((double)o->t);
@@ -2172,14 +2200,9 @@ static int basket_greeks_setup(mc_context *c, const typename BasketIn<Real>::typ
         inv_s[a] = (Real)(1.0 / (double)o->s[a]);
         vt[a] = (Real)(va * (double)o->t);
     }
-    const size_t bytes = host.size() * sizeof(Real);
-    std::vector<char> key(bytes + 2);
-    memcpy(key.data(), host.data(), bytes);
-    key[bytes] = (char)sizeof(Real);
-    key[bytes + 1] = LR ? 'R' : 'G';
     if (int rc = begin_call(c, c->stream)) return rc;
-    if (int rc = upload_table(c, c->stream, key, host.data(), bytes)) return rc;
-    k.consts = (const Real *)c->d_table;
+    if (int rc = c->table.upload(c, c->stream, table_key(host, LR ? 'R' : 'G'), host.data(), host.size() * sizeof(Real))) return rc;
+    k.consts = (const Real *)c->table.d;
     k.n = na;
     k.strike = o->k;
     k.sqrt_t = (Real)sqrt_t;
@@ -2323,8 +2346,7 @@ extern "C" int mc_cva_greeks_lr_run_f64(mc_context *c, const mc_cva_f64 *v, uint
 template <class Enq>
 static int run_sync(mc_context *c, uint64_t n, double discount, mc_result *out, Enq enqueue)
 {
-    using clock = std::chrono::steady_clock;
-    const auto ms_between = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    using clock = host_clock;
     // a caller that did part of the call's work before coming here (the staged launch-geometry form) has set call_t0
     const auto wall0 = c->call_t0_valid ? c->call_t0 : clock::now();
     if (!c->call_t0_valid)   // what earlier calls of other kinds (per-path dumps, Greeks, test hooks) left in the accumulators is not this call's
@@ -2335,10 +2357,7 @@ static int run_sync(mc_context *c, uint64_t n, double discount, mc_result *out, 
     float ms = 0;
     const double *h = c->h_triple;
     clock::time_point t_enqueued;
-    struct Scope {   // whatever way out: the stage accumulators and flags belong to ONE call
-        mc_context *c;
-        ~Scope() { c->acc_setup_ms = c->acc_table_ms = 0, c->stats_timed_call = false; }
-    } scope{c};
+    CallStatsScope scope{c};
     if (!c->timing && c->fused) {
         volatile double *flag = c->h_direct + 2;
         *flag = DIRECT_SENTINEL;
@@ -2381,33 +2400,10 @@ static int run_sync(mc_context *c, uint64_t n, double discount, mc_result *out, 
         if (c->timing) HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     }
     const auto t_result = clock::now();
-    if (!(h[2] == (double)n))   // also catches the poison (NaN) of a reduction that never closed
-        return fail(MC_ERR_HIP, "device returned n=%g, expected %llu: the call's final reduction did not complete", h[2],
-                    (unsigned long long)n);
-    out->sum = h[0];
-    out->sum2 = h[1];
-    out->n = (uint64_t)h[2];
-    out->kernel_ms = ms;
-    if (out->n != n)
-        return fail(MC_ERR_HIP, "device returned n=%llu, expected %llu", (unsigned long long)out->n,
-                    (unsigned long long)n);
-    mc_closing(out->sum, out->sum2, out->n, discount, &out->expected, &out->confidence);
+    if (int rc = close_triple(h, n, discount, ms, out)) return rc;
     const auto t_closed = clock::now();
     out->wall_ms = (float)ms_between(wall0, t_closed);
-    // the stage breakdown (mc_context_last_call_stats): consecutive host-clock intervals, the device's kernel time taken out of the wait
-    mc_call_stats &k = c->stats;
-    const double before = ms_between(wall0, t_enqueued), wait = ms_between(t_enqueued, t_result);
-    k.setup_ms = (float)c->acc_setup_ms;
-    k.table_upload_ms = (float)c->acc_table_ms;
-    k.launch_ms = (float)std::max(0.0, before - c->acc_setup_ms - c->acc_table_ms);
-    // the events' figure, capped at the host's wait: the opening event is stamped when the idle device reaches it, so on the FIRST launch
-    // of a kernel it also spans the code-object load the host spent inside the launch call (already counted in launch_ms)
-    k.kernel_ms = (float)std::min((double)ms, wait);
-    k.readback_ms = (float)std::max(0.0, wait - (double)k.kernel_ms);
-    k.closing_ms = (float)ms_between(t_result, t_closed);
-    k.wall_ms = out->wall_ms;
-    k.context_create_ms = c->create_ms;
-    k.first_call = c->sync_calls++ == 0;
+    record_call_stats(c, wall0, t_enqueued, t_result, t_closed, ms);
     return MC_OK;
 }
 
@@ -2467,7 +2463,7 @@ static int from_normals_run(mc_context *c, const Real *h_normals, size_t count, 
     if (rc == MC_OK && h_values)
         rc = dump_sync<Real>(c, n, h_values, [&](hipStream_t st, double *t, Real *d) { return enqueue(st, t, d); });
     c->ext = nullptr, c->ext_per_unit = 0, c->ext_flags = 0;
-    c->table_key.clear();   // a table built under the test switches must not be reused by a pricing call
+    c->table.key.clear();   // a table built under the test switches must not be reused by a pricing call
     return rc;
 }
 
@@ -2715,7 +2711,7 @@ static int grid_basket_fused(mc_context *c, const typename BasketIn<Real>::type 
 {
     BasketArgs<Real, NA> k;
     double out_scale = 1.0;
-    if (int rc = basket_fold<Real, NA>(c, *o, k, out_scale)) return rc;
+    if (int rc = basket_args<Real, NA>(c, *o, k, out_scale)) return rc;
     return grid_run_fused<Real>(c, nb, nt, ppb, (uint32_t)o->n, out_scale, out_scale * out_scale, std::exp(-(double)o->r * (double)o->t), h_values, out,
                                 [&](const Tail &t, const Work &w, const GridGeom &geo, int groups, int group, hipStream_t st, Real *d_out) -> int {
                                     if (d_out)
@@ -2766,8 +2762,7 @@ static int grid_basket(mc_context *c, const typename BasketIn<Real>::type *o, in
     uint64_t n;
     if (int rc = grid_check(c, o, nb, nt, ppb, h_values ? (const void *)h_values : (const void *)out, &n)) return rc;
     if (o->n < 1 || o->n > MC_MAX_ASSETS_GENERIC) return fail(MC_ERR_INVALID, "basket: bad n");
-    if (!o->s || !o->v || !o->p || !o->d || !o->w) return fail(MC_ERR_INVALID, "basket: NULL array");
-    if (!(o->t >= 0) || !std::isfinite((double)o->r) || !std::isfinite((double)o->k)) return fail(MC_ERR_INVALID, "basket: need t>=0 and finite r, k");
+    if (int rc = basket_check_inputs(o)) return rc;
     bool fused;
     if (int rc = grid_pick(c, grid_fused_fits(c, nb) && o->n <= 16, &fused)) return rc;
     if (!fused)
