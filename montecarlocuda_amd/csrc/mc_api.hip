@@ -1048,6 +1048,13 @@ template <> struct VanillaTraits<float> {
     static int launch_hot(mc_context *c, ProfileScope &prof, bool anti, const Opt &k, const Work &w, const Tail &tail, int grid,
                           hipStream_t st)
     {
+        if (gen_of(c, w, 4) == GEN_PHILOX) {   // a large segment: whole blocks of 8 units per lane (mc_launch_shape.hpp: vanilla_blocking)
+            const VanillaBlocking b = vanilla_blocking(w.unit_lo, w.n_units, (uint32_t)grid * GROUP);
+            if (b.blocked) {
+                launch_sim(prof, anti ? vanilla_f32_blocked_kernel<true> : vanilla_f32_blocked_kernel<false>, grid, st, tail, k, w, b);
+                return MC_OK;
+            }
+        }
         return with_anti_gen<GEN_PHILOX | GEN_XORWOW | GEN_EXTERNAL>(anti, gen_of(c, w, 4), [&](auto a, auto tag) {
             launch_sim(prof, vanilla_f32_kernel<decltype(a)::value, typename decltype(tag)::type>, grid, st, tail, k, w);
         });

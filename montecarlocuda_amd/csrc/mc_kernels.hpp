@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mc_reduce.hpp"
 #include "mc_rng.hpp"
 
@@ -98,8 +100,10 @@ __device__ __forceinline__ void box_muller_pk(uint32_t xa, uint32_t ya, uint32_t
 //
 // GenExternal (from-normals hooks, launch-geometry mode): the four normals come from memory and the exponent is fma(z, b2, a2k); everything after the
 // exponent -- exponential, clamp-subtract, sums, flushes, final reduction -- is the code of the hot path.
+//
+// `r` = the unit's four words when the caller has them already (vanilla_f32_blocked_kernel), else drawn from `gen`.
 template <bool ANTI, class Gen>
-__device__ __forceinline__ void vanilla_unit_pk(Gen &gen, const VanillaF32 &o, const Work &w, uint32_t c0, f2 &pc, f2 &ps)
+__device__ __forceinline__ void vanilla_unit_pk(Gen &gen, const VanillaF32 &o, const Work &w, uint32_t c0, f2 &pc, f2 &ps, const u32x4 *have = nullptr)
 {
     const f2 a = bcast(o.a2k);
     f2 yc, ys, mc_, ms_;   // exponents (log2 units) of the cos / sin branch paths and of their mirrors
@@ -110,7 +114,7 @@ __device__ __forceinline__ void vanilla_unit_pk(Gen &gen, const VanillaF32 &o, c
         yc = pk_fma(zc, b, a), ys = pk_fma(zs, b, a);
         mc_ = pk_fma(-zc, b, a), ms_ = pk_fma(-zs, b, a);
     } else {
-        const u32x4 r = gen.words(w, c0, 0u, 1u /*MC_DOMAIN_VANILLA*/);
+        const u32x4 r = have ? *have : gen.words(w, c0, 0u, 1u /*MC_DOMAIN_VANILLA*/);
         f2 rad, c, s;
         box_muller_pk(r.x, r.y, r.z, r.w, o.radius2, rad, c, s);
         yc = pk_fma(c, rad, a), ys = pk_fma(s, rad, a);
@@ -186,6 +190,107 @@ __global__ __launch_bounds__(GROUP) void vanilla_f32_kernel(const Tail /* first 
         vanilla_unit_pk<ANTI>(gen, o, w, c0, pc, ps);
         s2 += pc + ps;
         q2 += pc * pc + ps * ps;
+    }
+    acc_s += (double)(s2.x + s2.y);
+    acc_q += (double)(q2.x + q2.y);
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// f32, Philox, LARGE calls: a lane takes whole 8-aligned BLOCKS of 8 consecutive units, lane g blocks g, g + stride, ...
+// (a SWEEP of the grid = 8 stride units).  The eight units share the front of Philox (mc_rng.hpp: PhiloxBlock8), a block is
+// exactly one flush group -- its first unit initialises the fp32 partials, its end flushes them: no zeroing, no per-trip
+// flush test -- and the counter moves once per block: 481 VALU instructions per 8 units against the loop above's 500.  Same
+// payoffs bit for bit, added up in another grouping.  Which units run blocked is the host's decision (mc_launch_shape.hpp:
+// vanilla_blocking; it launches this kernel only where that pays): `sweeps` full sweeps, then lanes below `extra` take one
+// more block (the last, partial sweep); the units outside the blocks -- `head` of them below the first multiple of 8, the
+// others beyond the last block -- are unit-strided by the loop above, from the last lane down (those lanes took no block
+// in a partial sweep), `rest_trips` full trips and a partial one.
+struct VanillaBlocking {
+    uint32_t head;         // leading units below the first multiple of 8
+    uint32_t sweeps;       // full sweeps of blocks
+    uint32_t extra;        // blocks of the last, partial sweep; 0 = none
+    uint32_t blocked;      // units in blocks = 8 (sweeps stride + extra); 0 = the call runs vanilla_f32_kernel
+    uint32_t rest_trips;   // full unit-strided trips over the units beyond the last block: (n_units - head - blocked) / stride
+};
+
+// one unit into the fp32 partials; FIRST: the unit that begins a flush group initialises them (the same bits as adding to 0)
+template <bool FIRST> __device__ __forceinline__ void vanilla_f32_add(f2 pc, f2 ps, f2 &s2, f2 &q2)
+{
+    if constexpr (FIRST) {
+        s2 = pc + ps;
+        q2 = pk_fma(ps, ps, pc * pc);
+    } else {
+        s2 += pc;
+        s2 += ps;
+        q2 = pk_fma(pc, pc, q2);
+        q2 = pk_fma(ps, ps, q2);
+    }
+}
+
+// the 8 units of the block at `base` (8-aligned), flushed into the fp64 accumulators
+template <bool ANTI>
+__device__ __forceinline__ void vanilla_f32_block(GenPhilox &gen, const PhiloxBlock8 &px, const VanillaF32 &o, const Work &w, uint32_t base,
+                                                  double &acc_s, double &acc_q)
+{
+    const uint64_t shared = px.shared(base);
+    f2 s2, q2;
+    const auto unit = [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        const u32x4 r = px.template words<L>(shared);
+        f2 pc, ps;
+        vanilla_unit_pk<ANTI>(gen, o, w, base, pc, ps, &r);
+        vanilla_f32_add<L == 0>(pc, ps, s2, q2);
+    };
+    unit(std::integral_constant<int, 0>()), unit(std::integral_constant<int, 1>()), unit(std::integral_constant<int, 2>());
+    unit(std::integral_constant<int, 3>());
+    // left alone the scheduler issues all seven addend multiplies up front and runs out of registers (a spill in the loop):
+    // the second half of the block is scheduled on its own
+    __builtin_amdgcn_sched_barrier(0);
+    unit(std::integral_constant<int, 4>()), unit(std::integral_constant<int, 5>());
+    unit(std::integral_constant<int, 6>()), unit(std::integral_constant<int, 7>());
+    static_assert(VANILLA_F32_FLUSH == 8, "a block is one flush group");
+    acc_s += (double)(s2.x + s2.y);
+    acc_q += (double)(q2.x + q2.y);
+}
+
+template <bool ANTI>
+__global__ __launch_bounds__(GROUP) void vanilla_f32_blocked_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const VanillaF32 o, const Work w,
+                                                                    const VanillaBlocking b)
+{
+    const uint32_t stride = gridDim.x * GROUP;
+    uint32_t gtid = blockIdx.x * GROUP + threadIdx.x;
+    double acc_s = 0.0, acc_q = 0.0;
+    GenPhilox gen(w);
+    const PhiloxBlock8 px(w.unit_hi, 0u, 1u /*MC_DOMAIN_VANILLA*/, w.seed_lo, w.seed_hi);
+    uint32_t base = w.unit_lo + b.head + (gtid << 3);
+    for (uint32_t sweep = 0; sweep < b.sweeps; ++sweep, base += stride << 3)
+        vanilla_f32_block<ANTI>(gen, px, o, w, base, acc_s, acc_q);
+    // the lane's index again, from its block counter: one register less alive through the loop
+    asm volatile("" : "+v"(base));
+    gtid = (base - (w.unit_lo + b.head + ((b.sweeps * stride) << 3))) >> 3;
+    if (gtid < b.extra)
+        vanilla_f32_block<ANTI>(gen, px, o, w, base, acc_s, acc_q);
+    // the units beyond the last block, unit-strided from the last lane down (those lanes took no block in a partial sweep) ...
+    const uint32_t tail0 = w.unit_lo + b.head + b.blocked, n_tail = w.n_units - b.head - b.blocked, lane = stride - 1u - gtid;
+    f2 s2 = {0.0f, 0.0f}, q2 = {0.0f, 0.0f};   // at most 7 trips and a partial one: one flush group (the head units go to fp64 on their own)
+    uint32_t c0 = tail0 + lane;
+    for (uint32_t trip = 0; trip < b.rest_trips; ++trip, c0 += stride) {
+        f2 pc, ps;
+        vanilla_unit_pk<ANTI>(gen, o, w, c0, pc, ps);
+        vanilla_f32_add<false>(pc, ps, s2, q2);
+    }
+    if (b.rest_trips * stride + lane < n_tail) {
+        f2 pc, ps;
+        vanilla_unit_pk<ANTI>(gen, o, w, c0, pc, ps);
+        vanilla_f32_add<false>(pc, ps, s2, q2);
+    }
+    // ... and the `head` units below the first block, one each for the first lanes
+    if (gtid < b.head) {
+        f2 pc, ps;
+        vanilla_unit_pk<ANTI>(gen, o, w, w.unit_lo + gtid, pc, ps);
+        acc_s += (double)(pc.x + ps.x + pc.y + ps.y);
+        acc_q += (double)(pc.x * pc.x + ps.x * ps.x + pc.y * pc.y + ps.y * ps.y);
     }
     acc_s += (double)(s2.x + s2.y);
     acc_q += (double)(q2.x + q2.y);

@@ -70,6 +70,52 @@ static int grid_for_vanilla(int blocks, int compute_units, uint32_t n_units, int
     return (int)(want < (uint64_t)full ? want : (uint64_t)full);
 }
 
+// fp32 vanilla, Philox: which units of a segment run BLOCKED (mc_kernels.hpp: vanilla_f32_blocked_kernel -- a lane takes whole
+// 8-aligned blocks of 8 units, 481 VALU instructions per block against 500 for 8 unit-strided trips).  A block is 8 x coarser
+// than a unit, so the rule is written in unit-trips of the whole grid (stride = lanes of the launch; a SWEEP = 8 stride units):
+//   * the units below the first multiple of 8 (`head`, at most 7) are unit-strided;
+//   * every full sweep is blocked;
+//   * what is left after the last full sweep, R units, costs ceil(R / stride) trips unit-strided and 8 as one more, PARTIAL,
+//     sweep (lanes below the remaining block count take one block, the others wait): blocked only if R > 7.5 stride, else
+//     unit-strided in the same launch, from the last lane down.  So a call that ends just past a sweep leaves no lane behind
+//     an 8-unit straggler.  The 1e8-path call on the default grid (25 000 000 units, 2048 x 256 lanes) is 5 full sweeps +
+//     503 560 blocks (96 % of the lanes) in the sixth: every unit blocked;
+//   * a segment of less than vanilla_blocked_min_sweeps() = 1 full sweep is not blocked at all and runs vanilla_f32_kernel,
+//     the unit-strided loop alone, exactly as before.
+// Measured against the build before, alternating in one process (tools/c/ab_libs van32, event-bracketed launches on the
+// default grid, profiles/ab_vanilla_f32_blocked_sizes.log; a sweep is 16 777 216 paths):
+//     1e4 ... 1.5e7 paths (below one sweep, the same kernel as before)   -1.1 ... +2.4 %: the run-to-run spread of these calls
+//     1 sweep, 1 sweep + 64 units, 2 sweeps                              -3.4, -3.1 (-2.7 antithetic), -2.8 %
+//     1.5, 3.5, 5.5 sweeps (4 unit-strided trips after the sweeps)       -0.7, -2.0, -1.9 %
+//     1.9, 2.9 sweeps (7.2 unit-strided trips after the sweeps)          +0.4 ... +0.7, -1.0 %
+//     3.95 sweeps, 1e8 paths (5.96 sweeps; a partial sweep)              -1.1, -2.1 % (1e8 -+ 8 units -1.9, -1.8; antithetic -1.9 %)
+//   The first form -- ONE kernel that decided the split itself (three scalar divisions in its prologue) and took a partial
+//   sweep from 7 strides on, also without a full sweep -- cost the small calls +4.1, +1.8, +1.1, +1.6, +0.9 % at 1e4, 1e5, 1e6,
+//   4e6, 1e7 paths and +3.3 % at 1.5e7 (0.89 of a sweep, a partial sweep alone)
+//   [profiles/ab_vanilla_f32_blocked_first_form.log]: hence a kernel of its own above the limit, the split as a kernel
+//   argument, no blocks below one full sweep, and 7.5 strides before a partial sweep is taken.
+// MC_VANILLA_BLOCKED_MIN_SWEEPS moves the limit for experiments (0 = block whatever has a block; a large value = never).
+static uint32_t vanilla_blocked_min_sweeps()
+{
+    static const int v = env_int("MC_VANILLA_BLOCKED_MIN_SWEEPS", 1, 0, 1 << 30);
+    return (uint32_t)v;
+}
+static VanillaBlocking vanilla_blocking(uint32_t unit_lo, uint32_t n_units, uint32_t stride)
+{
+    VanillaBlocking b = {0, 0, 0, 0, 0};
+    const uint32_t head = (0u - unit_lo) & 7u;
+    if (stride == 0 || n_units < head + 8u)
+        return b;
+    const uint32_t n_blocks = (n_units - head) >> 3, sweeps = n_blocks / stride;
+    const uint64_t left_units = (uint64_t)(n_units - head) - 8ull * sweeps * stride;
+    const uint32_t extra = 2ull * left_units > 15ull * stride ? n_blocks - sweeps * stride : 0u;
+    if (sweeps < vanilla_blocked_min_sweeps() || sweeps + extra == 0)
+        return b;
+    b.head = head, b.sweeps = sweeps, b.extra = extra, b.blocked = 8u * (sweeps * stride + extra);
+    b.rest_trips = (n_units - head - b.blocked) / stride;
+    return b;
+}
+
 // Which kernel family prices a basket of n assets (measured on MI355X: tools/generic_basket_speed.py, runs
 // alternated in one gpurun call):
 //   n <= basket_static_max (fp32: 12, fp64: 8)

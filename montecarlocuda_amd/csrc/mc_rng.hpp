@@ -72,6 +72,62 @@ __device__ __forceinline__ u32x4 philox_unit(uint32_t unit_lo, uint32_t unit_hi,
     return philox4x32_10(unit_hi, unit_lo, block, domain, k0, k1);
 }
 
+// EIGHT consecutive units base .. base + 7 (base % 8 == 0) of one lane share the front of Philox.  Round 1 leaves one
+// lane-varying word, n0 = K ^ unit_lo with K = hi(M1 block) ^ k0 wave-uniform, and round 2's only vector multiply is
+// p0 = M0 n0: everything after depends on the unit through p0 alone.  For the eight units n0 = ((K & ~7) ^ base) + l with
+// l = (K & 7) ^ (unit_lo & 7) running over 0 .. 7 once each, so
+//     p0 = M0 ((K & ~7) ^ base) + M0 l            (exactly: it IS the product M0 n0 < 2^64)
+// -- one xor and one multiply per block of 8 (`shared`), and per unit ONE v_mad_u64_u32 with l as an inline constant and
+// the shared product as its 64-bit addend (`words<L>`; l = 0 is the shared product itself) where philox_unit spends a
+// counter add, round 1's v_bitop3_b32 and the same multiply with addend 0.  words<L> are the words of unit
+// base + (L ^ (K & 7)): a wave-uniform permutation inside the block, which a kernel that adds up all eight never sees.
+// The oracle twin is the plain generator: tests/test_philox_block8.py checks the identity word for word.
+//
+// hipcc re-associates `shared + M0 * L` back into M0 * (n | L) (a v_bitop3_b32 and a multiply with addend 0 per unit),
+// whether M0 is a literal or an opaque register, so the addend form is an asm.  Its operands need no wait states on
+// gfx950: an SGPR written by the scalar unit, an inline constant and a VGPR pair written by an ordinary (non-transcendental)
+// VALU instruction; the carry-out SGPR pair is never read.  The output is early-clobber: it must not overlap the addend.
+struct PhiloxBlock8 {
+    uint32_t c1, c2, c3;   // round 1's wave-uniform output words 1 .. 3
+    uint32_t k0, k1;       // round 2's key
+    uint32_t kb;           // K & ~7
+    uint32_t m0;           // PHILOX_M0 in a scalar register the compiler does not see through (the asm's "s" operand)
+    __device__ __forceinline__ PhiloxBlock8(uint32_t unit_hi, uint32_t block, uint32_t domain, uint32_t key0, uint32_t key1)
+    {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * unit_hi, p1 = (uint64_t)PHILOX_M1 * block;
+        kb = ((uint32_t)(p1 >> 32) ^ key0) & ~7u;
+        c1 = (uint32_t)p1, c2 = (uint32_t)(p0 >> 32) ^ domain ^ key1, c3 = (uint32_t)p0;
+        k0 = key0 + PHILOX_W0, k1 = key1 + PHILOX_W1;
+        m0 = PHILOX_M0;
+        asm volatile("" : "+s"(m0));
+    }
+    __device__ __forceinline__ uint64_t shared(uint32_t base) const { return (uint64_t)m0 * (kb ^ base); }
+    template <int L> __device__ __forceinline__ u32x4 words(uint64_t shared_p0) const
+    {
+        static_assert(L >= 0 && L < 8, "a block is 8 units");
+        uint64_t p0 = shared_p0;
+        if constexpr (L != 0) {
+            uint64_t carry;
+            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(p0), "=s"(carry) : "s"(m0), "n"(L), "v"(shared_p0));
+        }
+        // round 2 from its products, then rounds 3 .. 10 as philox4x32_10 runs them
+        const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+        uint32_t x0 = xor3((uint32_t)(p1 >> 32), c1, k0), x2 = xor3((uint32_t)(p0 >> 32), c3, k1);
+        uint32_t x1 = (uint32_t)p1, x3 = (uint32_t)p0;
+        uint32_t r0 = k0 + PHILOX_W0, r1 = k1 + PHILOX_W1;
+#pragma unroll
+        for (int round = 2; round < 10; ++round) {
+            const uint64_t q0 = (uint64_t)PHILOX_M0 * x0;
+            const uint64_t q1 = (uint64_t)PHILOX_M1 * x2;
+            const uint32_t n0 = xor3((uint32_t)(q1 >> 32), x1, r0);
+            const uint32_t n2 = xor3((uint32_t)(q0 >> 32), x3, r1);
+            x1 = (uint32_t)q1, x3 = (uint32_t)q0, x0 = n0, x2 = n2;
+            r0 += PHILOX_W0, r1 += PHILOX_W1;
+        }
+        return {x0, x1, x2, x3};
+    }
+};
+
 // ---- f32 ---------------------------------------------------------------------------------
 // u = x * 2^-32 + 2^-33  in (0, 1]   (one v_cvt_f32_u32 + one v_fma_f32)
 __device__ __forceinline__ float u01_f32(uint32_t x)

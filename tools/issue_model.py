@@ -178,8 +178,10 @@ def flush(every):
     return (f"fp32 partial sums flushed to fp64 every {every}th trip", lambda ops: n(ops, r"^v_cvt_f64_f32") > 0, 1.0 / every)
 
 
-def spec(pattern, units=None, dates_per_trip=None, rules=(), note=""):
-    return {"pattern": pattern, "units": units, "dates_per_trip": dates_per_trip, "rules": list(rules), "note": note}
+def spec(pattern, units=None, dates_per_trip=None, rules=(), note="", loop="all"):
+    """loop = "all": every loop that holds the generator is the hot path; "largest": of several such loops, the one with the
+    most Philox multiplies alone (a kernel that keeps a second, unit-strided loop for the units outside its blocks)"""
+    return {"pattern": pattern, "units": units, "dates_per_trip": dates_per_trip, "rules": list(rules), "note": note, "loop": loop}
 
 
 def cva_rules(philox_share, philox_blocks):
@@ -190,7 +192,10 @@ def cva_rules(philox_share, philox_blocks):
 
 
 WORKLOADS = {
-    "vanilla_f32": spec("vanilla_f32_kernelILb0ENS_9GenPhiloxEEE", units=4, rules=[flush(8)]),
+    # the fp32 vanilla kernels (mc_kernels.hpp: vanilla_f32_block): one trip of the hot loop is a BLOCK of 8 units = 32 paths that share
+    # the front of Philox and end in the flush of the fp32 partials (one basic block: no flush rule); the bench's 1e8-path launch runs
+    # every unit blocked (5 trips of the loop + its peeled copy for the partial sweep), the unit-strided loops beside it stay cold
+    "vanilla_f32": spec("vanilla_f32_blocked_kernelILb0EEE", units=32, loop="largest"),
     "vanilla_f64": spec("vanilla_kernelINS_10VanillaF64EdLb0ENS_9GenPhiloxEEE", units=8),
     "vanilla_f64_n32": spec("vanilla_kernelINS_10VanillaF64EdLb0ENS_13GenPhiloxF32NEEE", units=4),
     "basket4_f32": spec("basket_f32_kernelILi4ELb0ENS_9GenPhiloxEEE", units=2, rules=[DUMP, flush(8)]),
@@ -202,7 +207,7 @@ WORKLOADS = {
     "cva256_f32": spec("cva_kernelIfLb0ENS_9GenPhiloxEEE", dates_per_trip=4, note="lds_rows"),
     # secondary estimators (no performance record): antithetic = the ANTI instantiation of the same kernel (a unit is a
     # mirrored pair), control variate = the plain instantiation with its wave-uniform `cv` branches taken
-    "vanilla_f32_anti": spec("vanilla_f32_kernelILb1ENS_9GenPhiloxEEE", units=4, rules=[flush(8)]),
+    "vanilla_f32_anti": spec("vanilla_f32_blocked_kernelILb1EEE", units=32, loop="largest"),
     "basket16_f64_anti": spec("basket_tiled_kernelIdLi16ELb1ENS_9GenPhiloxEEE", units=1, rules=[DUMP], note="anti"),
     "basket16_f64_cv": spec("basket_tiled_kernelIdLi16ELb0ENS_9GenPhiloxEEE", units=1, rules=[DUMP], note="cv"),
 }
@@ -249,14 +254,16 @@ def main():
             if bk["header"] == bk["name"] and bk.get("parent"):
                 parent[bk["name"]] = bk["parent"]
         ph_headers = {bk["header"] for bk in blocks if bk["header"] and n(bk["ops"], PHILOX) >= 8}
+        if sp["loop"] == "largest":
+            ph_headers = {max(ph_headers, key=lambda h: sum(n(bk["ops"], PHILOX) for bk in blocks if bk["header"] == h))}
         depth_of = {bk["name"]: bk["depth"] for bk in blocks if bk["header"] == bk["name"]}
         # layout range of the loops that hold Philox, widened to the shallowest loop enclosing them (LLVM lays a loop out contiguously)
         idx = [i for i, bk in enumerate(blocks) if bk["header"] in ph_headers]
         lo_i, hi_i = min(idx), max(idx)
         top = min(blocks[i]["depth"] for i in range(lo_i, hi_i + 1) if blocks[i]["depth"] > 0)
-        while lo_i > 0 and blocks[lo_i - 1]["depth"] >= top and blocks[lo_i - 1]["header"]:
+        while sp["loop"] == "all" and lo_i > 0 and blocks[lo_i - 1]["depth"] >= top and blocks[lo_i - 1]["header"]:
             lo_i -= 1
-        while hi_i + 1 < len(blocks) and blocks[hi_i + 1]["depth"] >= top and blocks[hi_i + 1]["header"]:
+        while sp["loop"] == "all" and hi_i + 1 < len(blocks) and blocks[hi_i + 1]["depth"] >= top and blocks[hi_i + 1]["header"]:
             hi_i += 1
         loop = blocks[lo_i:hi_i + 1]
         header, depth = loop[0]["header"], top

@@ -260,6 +260,35 @@ __global__ __launch_bounds__(256) void k_philox_mix(float *out, unsigned long lo
     if (blockIdx.x == 0 && threadIdx.x == 0) { clk[0] = t1 - t0; clk[1] = w1 - w0; }
 }
 
+// v_mad_u64_u32 as the blocked Philox front issues it (mc_rng.hpp: PhiloxBlock8::words): scalar factor, INLINE-CONSTANT factor, a
+// non-zero 64-bit VGPR-pair addend, scalar-pair carry-out.  The hot loops only ever passed addend 0 before; MIX = 1 alternates it
+// with the addend-0 form, the company it keeps in the kernel.
+template <int MIX> __global__ __launch_bounds__(256) void k_mad_addend(float *out, unsigned long long *clk)
+{
+    unsigned long long r[8], p[8];
+    unsigned a[8];
+    for (int i = 0; i < 8; i++) { a[i] = threadIdx.x * 2654435761u + i; p[i] = ((unsigned long long)a[i] << 32) | (a[i] * 40503u); r[i] = 0; }
+    unsigned m = 0xD2511F53u;
+    asm volatile("" : "+s"(m));
+    unsigned long long t0 = __builtin_amdgcn_s_memtime(), w0 = __builtin_amdgcn_s_memrealtime();
+    for (int it = 0; it < ITERS; ++it) {
+        _Pragma("unroll") for (int u = 0; u < UNROLL; ++u) {
+            _Pragma("unroll") for (int i = 0; i < 8; i++) {
+                unsigned long long carry;
+                if (MIX && (i & 1))
+                    asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(r[i]) : "v"(a[i]), "s"(m) : "vcc");
+                else
+                    asm volatile("v_mad_u64_u32 %0, %1, %2, 3, %3" : "=&v"(r[i]), "=s"(carry) : "s"(m), "v"(p[i]));
+            }
+        }
+    }
+    unsigned long long t1 = __builtin_amdgcn_s_memtime(), w1 = __builtin_amdgcn_s_memrealtime();
+    unsigned long long s = 0;
+    for (int i = 0; i < 8; i++) s += r[i];
+    if (s == 123456ull) out[0] = 1.0f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { clk[0] = t1 - t0; clk[1] = w1 - w0; }
+}
+
 // same instruction multiset as k_philox_mix, but each dependent instruction is 8 instructions away
 __global__ __launch_bounds__(256) void k_philox_mix_far(float *out, unsigned long long *clk)
 {
@@ -383,6 +412,7 @@ int main(int argc, char **argv)
         {"v_alignbit_b32", k_alignbit}, {"v_mov_b32_dpp", k_mov_dpp},
         {"v_mul_u32_u24", k_mul_u32_u24}, {"v_mad_u32_u24", k_mad_u32_u24},
         {"v_mul_lo_u32", k_mul_lo_u32}, {"v_mul_hi_u32", k_mul_hi_u32}, {"v_mad_u64_u32", k_mad_u64_u32},
+        {"v_mad_u64 c,+v64", k_mad_addend<0>}, {"[mad c,+v64;mad] /2", k_mad_addend<1>},
         {"v_exp_f32", k_exp_f32}, {"v_log_f32", k_log_f32}, {"v_sin_f32", k_sin_f32}, {"v_cos_f32", k_cos_f32},
         {"v_sqrt_f32", k_sqrt_f32}, {"v_rcp_f32", k_rcp_f32}, {"v_rsq_f32", k_rsq_f32},
         {"v_pk_fma_f32", k_pk_fma_f32}, {"v_pk_mul_f32", k_pk_mul_f32}, {"v_pk_add_f32", k_pk_add_f32},
