@@ -67,6 +67,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_VANILLA 1u
 #define MC_DOMAIN_BASKET 2u
 #define MC_DOMAIN_CVA 3u
+#define MC_DOMAIN_ASIAN 4u
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -91,6 +92,15 @@ typedef struct {
 /* CVA of one call: dp/MonteCarlo.h:57-65 without the unused `ns`. */
 typedef struct { float defint, lgd; mc_option_f32 option; int n_grid; } mc_cva_f32;
 typedef struct { double defint, lgd; mc_option_f64 option; int n_grid; } mc_cva_f64;
+
+/* Arithmetic-average (Asian) call: n_dates equally spaced monitoring dates t_j = j t / n_dates, j = 1 ... n_dates (t_0 is not
+ * in the average).  Not in the reference.  The per-date constants ln S0 + j (r - v^2/2) dt travel as a table of one value per
+ * date, folded in fp64 and rounded once, which the kernels read through scalar loads: the cap keeps that table (16 KB in
+ * fp32, 32 KB in fp64) the size of the scalar data cache, and the fp32 running sums over the dates (rounding error
+ * ~ n_dates 2^-24 relative) at 2.4e-4 of the average in the worst case. */
+#define MC_MAX_ASIAN_DATES 4096
+typedef struct { mc_option_f32 option; int n_dates; } mc_asian_f32;
+typedef struct { mc_option_f64 option; int n_dates; } mc_asian_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -287,6 +297,34 @@ int mc_cva_run_f32(mc_context *ctx, const mc_cva_f32 *cva, uint64_t seed,
                    uint64_t first_path, uint64_t n_paths, mc_result *out);
 int mc_cva_run_f64(mc_context *ctx, const mc_cva_f64 *cva, uint64_t seed,
                    uint64_t first_path, uint64_t n_paths, mc_result *out);
+
+/* ---- arithmetic-average (Asian) call -------------------------------------------------------------
+ * Payoff max(A - K, 0), A = (1/m) sum_j S(t_j) over the m = n_dates monitoring dates; GBM walked date by date, one lane per
+ * path: ln S_j = ln S0 + j a + bx W_j, a = (r - v^2/2) dt, bx = v sqrt(dt), W_j = z_1 + ... + z_j.  Stream: path p is unit p
+ * of MC_DOMAIN_ASIAN, date j (1-based) draws entry (j - 1) % npb of block (j - 1) / npb (npb = 4 in f32, 8 in f64): the CVA's
+ * layout under its own domain word, so a path's value depends on (seed, global path index, inputs) only.  Path ranges as
+ * for the CVA (a unit is a path).
+ * Estimator switches: mc_context_set_antithetic (mean of the value at z and at -z; n counts pairs) and
+ * mc_context_set_control_variate -- the per-path value becomes max(A - K, 0) - max(G - K, 0), G = exp((1/m) sum_j ln S_j) the
+ * geometric average on the same normals; G is lognormal, mc_asian_control_mean_* returns E[max(G - K, 0)] (fp64,
+ * undiscounted):  exp(mu + s2/2) Phi(d1) - K Phi(d2),  mu = ln S0 + a (m + 1)/2,  s2 = v^2 dt (m + 1)(2m + 1)/(6m),
+ * d1 = (mu - ln K + s2)/sqrt(s2), d2 = d1 - sqrt(s2).  mc_asian_run_* adds it back (expected = discount * (sum/n + mean));
+ * users of mc_asian_launch_* do the same after their all-reduce.  The two switches combine.
+ * Several GPUs: mc_asian_launch_* on the ranges of mc_shard_range, the triples added, mc_closing (plus the control mean).
+ * MC_ERR_INVALID before anything is enqueued: n_dates outside [1, MC_MAX_ASIAN_DATES], s <= 0, t <= 0, v < 0, a non-finite
+ * input, with the control variate on k <= 0 or v == 0, and the range errors of the other products.  MC_ERR_UNSUPPORTED: a
+ * XORWOW context (one sequence per lane is another sample definition), MC_NORMALS_F32 on the _f64 calls.  The context
+ * stays usable.  mc_asian_paths_* returns the per-path values (undiscounted; n_paths <= 2^26). */
+int mc_asian_run_f32(mc_context *ctx, const mc_asian_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_asian_run_f64(mc_context *ctx, const mc_asian_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_asian_launch_f32(mc_context *ctx, const mc_asian_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                        double *d_triple, void *stream);
+int mc_asian_launch_f64(mc_context *ctx, const mc_asian_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                        double *d_triple, void *stream);
+int mc_asian_paths_f32(mc_context *ctx, const mc_asian_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_asian_paths_f64(mc_context *ctx, const mc_asian_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_asian_control_mean_f32(const mc_asian_f32 *opt, double *mean);
+int mc_asian_control_mean_f64(const mc_asian_f64 *opt, double *mean);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

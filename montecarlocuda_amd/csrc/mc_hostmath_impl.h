@@ -100,3 +100,27 @@ int FN(mc_basket_control_mean)(const BASKET *o, double *mean)
     *mean = exp(m + 0.5 * var) * 0.5 * erfc(-d1 / sqrt(2.0)) - (double)o->k * 0.5 * erfc(-d2 / sqrt(2.0));
     return MC_OK;
 }
+
+/* E[max(G - K, 0)] of the geometric-average control of the Asian call, closed form in fp64 (see mc_mi355x.h):
+ * ln G = ln S0 + a (m + 1)/2 + (bx/m) sum_j W_j, and sum_j W_j = sum_i (m - i + 1) z_i has variance m (m + 1)(2m + 1)/6 */
+int FN(mc_asian_control_mean)(const ASIAN *o, double *mean)
+{
+    if (!o || !mean)
+        return mc_internal_fail(MC_ERR_INVALID, "asian control variate: NULL argument");
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    if (o->n_dates < 1 || o->n_dates > MC_MAX_ASIAN_DATES)
+        return mc_internal_fail(MC_ERR_INVALID, "asian: n_dates=%d outside [1, %d]", o->n_dates, MC_MAX_ASIAN_DATES);
+    if (!(s > 0) || !(t > 0) || !isfinite(s) || !isfinite(t) || !isfinite(r) || !isfinite(v) || !isfinite(k))
+        return mc_internal_fail(MC_ERR_INVALID, "asian: need s>0, t>0 and finite inputs");
+    if (!(k > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "asian control variate: needs k > 0");
+    if (!(v > 0))
+        return mc_internal_fail(MC_ERR_INVALID, v == 0 ? "asian control variate: needs v != 0 (v == 0 leaves nothing to control)"
+                                                       : "asian: need v >= 0");
+    const double m = (double)o->n_dates, dt = t / m;
+    const double mu = log(s) + (r - 0.5 * v * v) * dt * (m + 1.0) * 0.5;
+    const double var = v * v * dt * (m + 1.0) * (2.0 * m + 1.0) / (6.0 * m), sd = sqrt(var);
+    const double d1 = (mu - log(k) + var) / sd, d2 = d1 - sd;
+    *mean = exp(mu + 0.5 * var) * 0.5 * erfc(-d1 / sqrt(2.0)) - k * 0.5 * erfc(-d2 / sqrt(2.0));
+    return MC_OK;
+}

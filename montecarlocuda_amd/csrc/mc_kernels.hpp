@@ -1818,6 +1818,165 @@ __global__ __launch_bounds__(GROUP) void cva_kernel(const Tail /* first argument
 }
 
 // =========================================================================================
+// Arithmetic-average (Asian) call on m equally spaced dates, with the geometric average as control variate.  Not in the
+// reference.  The walk is cva_path's -- W_j = z_1 + ... + z_j the lane's only state, ln S_j = fma(W_j, bx, xk_j) with
+// xk_j = ln S0 + j a from a per-date table (fp64 on the host, rounded once; wave-uniform j: scalar loads, so xk_j is the
+// scalar operand of the fma and costs the vector pipe nothing) -- and a date's work is a strict subset of the CVA's: ONE
+// exponential, no Hastings tails.  Per path:
+//   A = (1/m) sum_j S_j,   value = (A - K)^+
+//   CV:   G = E(g0 + g1 sum_j W_j)  (= exp((1/m) sum_j ln S_j): one add per date, one exponential per path),  value -= (G - K)^+
+//   ANTI: the same at -z (W -> -W: a second exponential per date, -sum W for the mirrored G), value = mean of the two
+// Stream: domain 4, date j (0-based here) = entry j % NPB of block j / NPB: the CVA layout.
+// =========================================================================================
+template <class Real>
+struct AsianArgs {
+    const Real *xk;   // n_dates values: (ln S0 + (j + 1) a) in exponent units (natural log in f64, log2 in f32)
+    int n_dates;
+    Real bx;          // v sqrt(dt) in exponent units
+    Real strike;
+    Real inv_m;       // 1 / n_dates
+    Real g0, g1;      // ln G = g0 + g1 sum_j W_j in exponent units: g0 = ln S0 + a (m + 1) / 2, g1 = bx / m
+};
+
+template <class Real>
+__device__ __forceinline__ Real asian_value(Real sum, Real sw, const AsianArgs<Real> &o, bool cv)
+{
+    const Real a = fma_r(sum, o.inv_m, -o.strike);
+    Real val = a > 0 ? a : 0;
+    if (cv) {
+        const Real g = exp_model(fma_r(sw, o.g1, o.g0)) - o.strike;
+        val -= g > 0 ? g : 0;
+    }
+    return val;
+}
+
+// fp32: a block of four normals = two packed date pairs per trip, as cva_path<float>: Wp = {W + z0, W + z0 + z1}, one
+// v_pk_fma_f32 for the pair's ln2 S (its addend the pair's {xk, xk'} straight from two adjacent SGPRs), two v_exp_f32, one packed add
+// into the even / odd halves of sum S, and under CV one packed add into sum W.
+template <bool ANTI, bool CV, class Gen>
+__device__ __forceinline__ float asian_path(Gen &gen, const AsianArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two packed date pairs per block");
+    const int n = o.n_dates;
+    // bx in a vector register pair for the whole path: a packed fma reads ONE scalar operand, and that is the pair's {xk, xk'}
+    // (left to itself hipcc keeps bx scalar and copies every xk pair into vector registers: 3 v_mov per four dates)
+    f2 bx = bcast(o.bx);
+    asm("" : "+v"(bx));
+    float W = 0;
+    f2 sum = {0.0f, 0.0f}, sum_m = {0.0f, 0.0f}, sw = {0.0f, 0.0f};   // even / odd dates
+    float z[NPB];
+    auto pair = [&](int j, float z0, float z1) {
+        const f2 Wp = {W + z0, (W + z0) + z1};
+        W = Wp.y;
+        const f2 xk = {o.xk[j], o.xk[j + 1]};
+        sum += pk_exp2(pk_fma(Wp, bx, xk));
+        if (ANTI)
+            sum_m += pk_exp2(pk_fma(-Wp, bx, xk));
+        if (CV)
+            sw += Wp;
+    };
+    int j0 = 0;
+    for (; j0 + NPB <= n; j0 += NPB) {
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 4u /*MC_DOMAIN_ASIAN*/, z);
+        pair(j0, z[0], z[1]);
+        pair(j0 + 2, z[2], z[3]);
+    }
+    if (j0 < n) {   // wave-uniform: one to three dates left
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 4u /*MC_DOMAIN_ASIAN*/, z);
+        if (j0 + 2 <= n) {
+            pair(j0, z[0], z[1]);
+            j0 += 2;
+        }
+        if (j0 < n) {
+            W += j0 & 2 ? z[2] : z[0];
+            const float xk = o.xk[j0];
+            sum.x += __builtin_amdgcn_exp2f(__builtin_fmaf(W, o.bx, xk));
+            if (ANTI)
+                sum_m.x += __builtin_amdgcn_exp2f(__builtin_fmaf(-W, o.bx, xk));
+            if (CV)
+                sw.x += W;
+        }
+    }
+    const float sw1 = sw.x + sw.y;
+    float val = asian_value(sum.x + sum.y, sw1, o, CV);
+    if (ANTI)
+        val = 0.5f * (val + asian_value(sum_m.x + sum_m.y, -sw1, o, CV));
+    return val;
+}
+
+// fp64: dates in Box-Muller pairs through the generator's pair cursor, four pairs per trip for the bulk (the cursor's phase a
+// compile-time constant in each copy), one pair per trip for the rest: cva_path<double>'s loop.  bx (and -bx for the mirrored
+// path) sit in vector registers for the whole path, so ln S = fma(W, bx, xk_j) reads xk_j from its SGPR pair.
+template <bool ANTI, bool CV, class Gen>
+__device__ __forceinline__ double asian_path(Gen &gen, const AsianArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.n_dates;
+    double W = 0, s_a = 0, s_b = 0, m_a = 0, m_b = 0, sw = 0;   // sum S over even / odd dates, the same for the mirrored path, sum W
+    const double bx_v = to_vgpr(o.bx);
+    [[maybe_unused]] const double nbx_v = to_vgpr(-o.bx);
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto date = [&](int j, double z, double &s, double &m) {
+        W += z;
+        const double xk = o.xk[j];
+        s += exp_f64(fma_scalar_addend(W, bx_v, xk));
+        if (ANTI)
+            m += exp_f64(fma_scalar_addend(W, nbx_v, xk));
+        if (CV)
+            sw += W;
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 8 <= n; j += 8) {
+            const uint32_t g4 = (uint32_t)(j >> 3) << 2;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                double z0, z1;
+                gen.pair(w, c0, 4u /*MC_DOMAIN_ASIAN*/, g4 | k, carry, z0, z1);
+                date(j + 2 * (int)k, z0, s_a, m_a);
+                date(j + 2 * (int)k + 1, z1, s_b, m_b);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; j += 2) {
+        double z0, z1;
+        gen.pair(w, c0, 4u /*MC_DOMAIN_ASIAN*/, (uint32_t)(j >> 1), carry, z0, z1);
+        date(j, z0, s_a, m_a);
+        if (j + 1 < n)   // wave-uniform
+            date(j + 1, z1, s_b, m_b);
+    }
+    gen.pairs_done((uint32_t)((n + 1) >> 1));
+    double val = asian_value(s_a + s_b, sw, o, CV);
+    if (ANTI)
+        val = 0.5 * (val + asian_value(m_a + m_b, -sw, o, CV));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths
+template <class Real, bool ANTI, bool CV, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void asian_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const AsianArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = asian_path<ANTI, CV>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // CVA, parallel in the DATE axis.  Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
 // its path.  With the reformulation above the lane's only state is W_j = z_1 + ... + z_j and everything else is a table
 // row of the date, so the walk is a prefix sum followed by independent work: here a path's dates are shared by

@@ -102,6 +102,13 @@ def _as_cva(X, c) -> C.Structure:
     return _lib.CVA[X](c.defInt, c.lgd, _as_option(X, c.option), c.n)
 
 
+def _as_asian(X, a, n_dates=None) -> C.Structure:
+    """mc_asian_*: an option (OptionData or dict) with n_dates, or a dict that carries "n_dates" itself."""
+    if n_dates is None:
+        n_dates = a["n_dates"]
+    return _lib.ASIAN[X](_as_option(X, a), int(n_dates))
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -166,7 +173,7 @@ class Engine:
         check(lib().mc_context_set_antithetic(self._ctx, 1 if on else 0))
 
     def set_control_variate(self, on: bool):
-        """Baskets: simulate payoff(arithmetic) - payoff(geometric) and add the geometric closed form back."""
+        """Baskets and Asian calls: simulate payoff(arithmetic) - payoff(geometric) and add the geometric closed form back."""
         check(lib().mc_context_set_control_variate(self._ctx, 1 if on else 0))
 
     def order(self, stream: int):
@@ -342,6 +349,11 @@ class Engine:
     def cva(self, c, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
         return self._run("cva", precision, _as_cva(precision, c), seed, first_path, n_paths)
 
+    def asian(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """Arithmetic-average call over n_dates equally spaced dates (mc_asian_run_*); honours set_antithetic and
+        set_control_variate (the geometric-average control's closed-form mean is added back)."""
+        return self._run("asian", precision, _as_asian(precision, opt, n_dates), seed, first_path, n_paths)
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
@@ -357,6 +369,8 @@ class Engine:
         if prod == "basket":
             h = _BasketHolder(precision, inputs)
             return h.struct, h
+        if prod == "asian":   # inputs: the option's fields plus "n_dates"
+            return _as_asian(precision, inputs), None
         return _as_cva(precision, inputs), None
 
     # ---- per-path values (parity tests) ------------------------------------------------
@@ -375,6 +389,9 @@ class Engine:
 
     def cva_paths(self, c, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("cva", precision, _as_cva(precision, c), seed, first_path, n_paths)
+
+    def asian_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("asian", precision, _as_asian(precision, opt, n_dates), seed, first_path, n_paths)
 
     def normals(self, seed, domain, first_unit, n_units, block=0, precision="f64"):
         npb = 4 if (precision == "f32" or self._normals_f32) else 8
@@ -469,6 +486,13 @@ def basket_control_mean(b, precision="f64"):
     h = _BasketHolder(precision, b)
     m = C.c_double()
     check(getattr(lib(), f"mc_basket_control_mean_{precision}")(C.byref(h.struct), C.byref(m)))
+    return m.value
+
+
+def asian_control_mean(opt, n_dates, precision="f64"):
+    """Closed-form E[max(G - K, 0)] of the Asian call's geometric-average control (undiscounted, fp64)."""
+    m = C.c_double()
+    check(getattr(lib(), f"mc_asian_control_mean_{precision}")(C.byref(_as_asian(precision, opt, n_dates)), C.byref(m)))
     return m.value
 
 
