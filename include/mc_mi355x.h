@@ -68,6 +68,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_BASKET 2u
 #define MC_DOMAIN_CVA 3u
 #define MC_DOMAIN_ASIAN 4u
+#define MC_DOMAIN_BARRIER 5u
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -101,6 +102,16 @@ typedef struct { double defint, lgd; mc_option_f64 option; int n_grid; } mc_cva_
 #define MC_MAX_ASIAN_DATES 4096
 typedef struct { mc_option_f32 option; int n_dates; } mc_asian_f32;
 typedef struct { mc_option_f64 option; int n_dates; } mc_asian_f64;
+
+/* Single-barrier European call on n_dates equally spaced dates (the Asian call's dates), monitored on those dates only
+ * (MC_MONITOR_DISCRETE) or continuously, by the Brownian-bridge survival probability between them (MC_MONITOR_CONTINUOUS).
+ * Not in the reference.  The per-date constants sgn (ln B - ln S0 - j a) travel as the Asian call's table does: same cap,
+ * same cache argument. */
+#define MC_MAX_BARRIER_DATES 4096
+enum { MC_BARRIER_UP_OUT = 0, MC_BARRIER_UP_IN = 1, MC_BARRIER_DOWN_OUT = 2, MC_BARRIER_DOWN_IN = 3 };
+enum { MC_MONITOR_DISCRETE = 0, MC_MONITOR_CONTINUOUS = 1 };
+typedef struct { mc_option_f32 option; float barrier; int n_dates, type, monitoring; } mc_barrier_f32;
+typedef struct { mc_option_f64 option; double barrier; int n_dates, type, monitoring; } mc_barrier_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -325,6 +336,39 @@ int mc_asian_paths_f32(mc_context *ctx, const mc_asian_f32 *opt, uint64_t seed, 
 int mc_asian_paths_f64(mc_context *ctx, const mc_asian_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 int mc_asian_control_mean_f32(const mc_asian_f32 *opt, double *mean);
 int mc_asian_control_mean_f64(const mc_asian_f64 *opt, double *mean);
+
+/* ---- single-barrier call: discrete and Brownian-bridge continuous monitoring --------------------------
+ * The Asian call's walk on m = n_dates dates: dt = t/m, a = (r - v^2/2) dt, bx = v sqrt(dt), W_j = z_1 + ... + z_j,
+ * x_j = ln S_j = ln S0 + j a + bx W_j, x_0 = ln S0.  With h = ln barrier and sgn = +1 (up) or -1 (down) the distance to the
+ * barrier is d_j = sgn (h - x_j), in natural-log units; the path is on the live side at date j when d_j > 0.
+ *   discrete:    P = [min_{1<=j<=m} d_j > 0]                                  (t_0 is not monitored)
+ *   continuous:  P = [min_j d_j > 0] prod_{j=1..m} (1 - exp(-2 d_{j-1} d_j / bx^2)),   d_0 = sgn (h - ln S0):
+ *                the probability that the Brownian bridge between two monitored points stays on the live side, so the
+ *                estimator is unbiased for the continuously monitored price at ANY n_dates, even 1, and needs no extra
+ *                normals.  mc_barrier_closed_form_* is that price (Reiner-Rubinstein; discounted, no dividend, no rebate;
+ *                fp64; ignores n_dates and monitoring; usable without a GPU; also needs k > 0 and v > 0).
+ *   per-path value, undiscounted:  knock-out P (S_T - K)^+,  knock-in (1 - P)(S_T - K)^+,  S_T = exp(x_m).  On a path that
+ *   crossed at a date the knock-out value is exactly 0 and the knock-in value exactly the payoff.
+ * Stream: path p is unit p of MC_DOMAIN_BARRIER, date j (1-based) draws entry (j - 1) % npb of block (j - 1) / npb: the
+ * Asian layout under its own domain word.  mc_context_set_antithetic: the mean of the value at z and at -z; n counts pairs.
+ * Path ranges, the finish, timing, arming and ordering as for the other products; several GPUs as for the Asian call.
+ * MC_ERR_INVALID before anything is enqueued: n_dates outside [1, MC_MAX_BARRIER_DATES]; type or monitoring out of range;
+ * s <= 0, t <= 0, v < 0, barrier <= 0 or a non-finite input; the spot on or beyond the barrier (up with s >= barrier, down
+ * with s <= barrier: the product is then the vanilla call or nothing); continuous monitoring with v == 0; the range errors
+ * of the other products.  MC_ERR_UNSUPPORTED: a XORWOW context, MC_NORMALS_F32 on the _f64 calls, the control variate
+ * switched on (no candidate control reduces the variance with coefficient 1), a context set up for external normals or
+ * the launch geometry.  The context stays usable.  No rebate, puts, double barriers, unequal dates or Greeks.
+ * mc_barrier_paths_* returns the per-path values (undiscounted; n_paths <= 2^26). */
+int mc_barrier_run_f32(mc_context *ctx, const mc_barrier_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_barrier_run_f64(mc_context *ctx, const mc_barrier_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_barrier_launch_f32(mc_context *ctx, const mc_barrier_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                          double *d_triple, void *stream);
+int mc_barrier_launch_f64(mc_context *ctx, const mc_barrier_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                          double *d_triple, void *stream);
+int mc_barrier_paths_f32(mc_context *ctx, const mc_barrier_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_barrier_paths_f64(mc_context *ctx, const mc_barrier_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_barrier_closed_form_f32(const mc_barrier_f32 *opt, double *price);
+int mc_barrier_closed_form_f64(const mc_barrier_f64 *opt, double *price);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

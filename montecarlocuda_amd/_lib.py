@@ -15,8 +15,11 @@ LEGACY = {"f64": os.path.join(CSRC, "libmcgpu_f64.so"), "f32": os.path.join(CSRC
 
 MC_OK = 0
 MC_DEFAULT_SEED = 0x4D435F4D49333535
-DOMAIN_VANILLA, DOMAIN_BASKET, DOMAIN_CVA, DOMAIN_ASIAN = 1, 2, 3, 4
+DOMAIN_VANILLA, DOMAIN_BASKET, DOMAIN_CVA, DOMAIN_ASIAN, DOMAIN_BARRIER = 1, 2, 3, 4, 5
 MAX_ASIAN_DATES = 4096   # MC_MAX_ASIAN_DATES
+MAX_BARRIER_DATES = 4096   # MC_MAX_BARRIER_DATES
+BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
+MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
 MAX_ASSETS = 16          # register-resident basket kernels
 MAX_ASSETS_GENERIC = 64  # LDS-staged generic kernel beyond that
 NPB = {"f32": 4, "f64": 8}   # normals per block of the stream (include/mc_mi355x.h: MC_STREAM_VERSION 2)
@@ -65,6 +68,14 @@ class AsianF64(C.Structure):   # mc_asian_f64
     _fields_ = [("option", OptionF64), ("n_dates", C.c_int)]
 
 
+class BarrierF32(C.Structure):   # mc_barrier_f32
+    _fields_ = [("option", OptionF32), ("barrier", C.c_float), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
+
+
+class BarrierF64(C.Structure):   # mc_barrier_f64
+    _fields_ = [("option", OptionF64), ("barrier", C.c_double), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
+
+
 class Result(C.Structure):
     _fields_ = [("expected", C.c_double), ("confidence", C.c_double), ("sum", C.c_double), ("sum2", C.c_double),
                 ("n", C.c_uint64), ("kernel_ms", C.c_float), ("wall_ms", C.c_float)]
@@ -101,6 +112,7 @@ MAX_BOOK = 1 << 20   # MC_MAX_BOOK
 BASKET = {"f32": BasketF32, "f64": BasketF64}
 CVA = {"f32": CvaF32, "f64": CvaF64}
 ASIAN = {"f32": AsianF32, "f64": AsianF64}
+BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -120,6 +132,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_vanilla_greeks2_run_{_x}", f"mc_basket_gamma_run_{_x}"]
     EXPORTS += [f"mc_vanilla_book_run_{_x}", f"mc_vanilla_book_launch_{_x}"]
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
+    EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -196,6 +209,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_asian_run_{X}").argtypes = [ctx, C.POINTER(ASIAN[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_asian_paths_{X}").argtypes = [ctx, C.POINTER(ASIAN[X]), u64, u64, u64, RP]
         getattr(L, f"mc_asian_control_mean_{X}").argtypes = [C.POINTER(ASIAN[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_barrier_launch_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_barrier_run_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_barrier_paths_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_barrier_closed_form_{X}").argtypes = [C.POINTER(BARRIER[X]), C.POINTER(C.c_double)]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

@@ -84,7 +84,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a generic basket's folded constants, a basket's Greeks table
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // generator: Philox (counter-based, stateless) or XORWOW (one sequence per lane: mc_rng.hpp GenXorwow)
@@ -363,12 +363,12 @@ extern "C" int mc_context_describe(const mc_context *c, char *buf, int len)
     snprintf(buf, (size_t)len,
              "mc_context config: device=%d \"%s\" CUs=%d clock_mhz=%d blocks=%d finish=%s f64_normals=%s rng=%s antithetic=%d control_variate=%d timing=%d "
              "grid_form=%s basket_static_max=f32:%d,f64:%d basket_tiled_min=%d basket_mfma=%d grid_sub=%d(0=auto) vanilla_units_per_lane=%d cva_date_lanes=%d(0=auto) "
-             "asian_dates_max=%d created_in_ms=%.1f",
+             "asian_dates_max=%d barrier_dates_max=%d created_in_ms=%.1f",
              c->device, c->name, c->compute_units, c->clock_mhz, c->blocks, c->fused ? "fused" : "kernel", c->normals_f32 ? "f32" : "native",
              c->rng == MC_RNG_XORWOW ? "xorwow" : "philox", (int)c->antithetic, (int)c->control, (int)c->timing,
              c->grid_form == MC_GRID_FORM_STAGED ? "staged" : (c->grid_form == MC_GRID_FORM_FUSED ? "fused" : "auto"), basket_static_max<float>(),
              basket_static_max<double>(), basket_tiled_min(), (int)basket_mfma(), env_int("MC_GRID_SUB", 0, 0, 32), vanilla_units_per_lane(), c->cva_date_lanes,
-             MC_MAX_ASIAN_DATES, c->create_ms);
+             MC_MAX_ASIAN_DATES, MC_MAX_BARRIER_DATES, c->create_ms);
     return MC_OK;
 }
 
@@ -2225,6 +2225,85 @@ static int asian_enqueue(mc_context *c, const typename AsianIn<Real>::type *v, u
 }
 
 // ---------------------------------------------------------------------------------------
+// Single-barrier call, discrete or Brownian-bridge continuous monitoring: barrier_kernel, one lane per path
+// ---------------------------------------------------------------------------------------
+template <class Real> struct BarrierIn;
+template <> struct BarrierIn<float> { using type = mc_barrier_f32; };
+template <> struct BarrierIn<double> { using type = mc_barrier_f64; };
+static int barrier_check(const mc_barrier_f32 &o, int need_vol) { return mc_barrier_check_f32(&o, need_vol); }
+static int barrier_check(const mc_barrier_f64 &o, int need_vol) { return mc_barrier_check_f64(&o, need_vol); }
+
+// The range check, the constants folded in fp64 and rounded once, and the per-date table dk_j = sgn (ln B - ln S0 - j a)
+// (natural-log units), j = 1 ... n_dates, in the context's table buffer: cached by content, uploaded only when the inputs
+// change.  The direction of the barrier lives in the table and in the sign of dbx; knock-in / knock-out in (c0, c1).
+template <class Real>
+static int barrier_table_ready(mc_context *c, const typename BarrierIn<Real>::type *v, hipStream_t st, BarrierArgs<Real> &args)
+{
+    const auto &o = v->option;
+    const double sc = exp_scale<Real>();
+    const double m = (double)v->n_dates, dt = (double)o.t / m;
+    const double a = ((double)o.r - 0.5 * (double)o.v * (double)o.v) * dt, bx = (double)o.v * std::sqrt(dt), ln_s0 = std::log((double)o.s);
+    const double sgn = v->type <= MC_BARRIER_UP_IN ? 1.0 : -1.0, gap = std::log((double)v->barrier) - ln_s0;
+    // as for the Asian call: only the hard limit of the device's exp is enforced; below it an honest overflow of the spot gives inf
+    if (!(std::fabs(ln_s0) + std::fabs(gap) + m * (std::fabs(a) + bx * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+        return fail(MC_ERR_INVALID, "barrier: drift and volatility put the simulated spot outside the range of a double");
+    static thread_local std::vector<Real> tab;
+    tab.resize((size_t)v->n_dates);
+    for (int j = 1; j <= v->n_dates; ++j)
+        tab[(size_t)j - 1] = (Real)(sgn * (gap - (double)j * a));
+    if (int rc = c->table.upload(c, st, table_key(tab, 'R'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    const bool in = v->type == MC_BARRIER_UP_IN || v->type == MC_BARRIER_DOWN_IN;
+    args.dk = (const Real *)c->table.d;
+    args.n_dates = v->n_dates;
+    args.dbx = (Real)(-sgn * bx);
+    args.d0 = (Real)(sgn * gap);
+    args.cexp = v->monitoring == MC_MONITOR_CONTINUOUS ? (Real)(-2.0 / (bx * bx) * sc) : (Real)0;
+    args.xT = (Real)((ln_s0 + m * a) * sc);
+    args.bxe = (Real)(bx * sc);
+    args.strike = o.k;
+    args.c0 = in ? (Real)1 : (Real)0;
+    args.c1 = in ? (Real)-1 : (Real)1;
+    return MC_OK;
+}
+
+template <class Real>
+static int barrier_enqueue(mc_context *c, const typename BarrierIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                           double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "barrier: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "barrier: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "barrier: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_UNSUPPORTED, "barrier: no control variate (none of the candidates reduces the variance with coefficient 1)");
+    if (int rc = barrier_check(*v, v->monitoring == MC_MONITOR_CONTINUOUS)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    BarrierArgs<Real> args;
+    if (int rc = barrier_table_ready<Real>(c, v, st, args)) return rc;
+    const bool cont = v->monitoring == MC_MONITOR_CONTINUOUS;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) {
+                if (cont) launch_sim(prof, barrier_kernel<Real, true, true>, g, st, t, args, w, dst);
+                else      launch_sim(prof, barrier_kernel<Real, true, false>, g, st, t, args, w, dst);
+            } else {
+                if (cont) launch_sim(prof, barrier_kernel<Real, false, true>, g, st, t, args, w, dst);
+                else      launch_sim(prof, barrier_kernel<Real, false, false>, g, st, t, args, w, dst);
+            }
+            return MC_OK;
+        });
+}
+
+// ---------------------------------------------------------------------------------------
 // Greeks of the basket call and of the CVA: secondary kernels, plain estimator, synchronous
 // ---------------------------------------------------------------------------------------
 // the inputs' checks and the constant table of basket_greeks_kernel (and, LR = true, of basket_gamma_kernel), uploaded
@@ -3033,6 +3112,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return asian_enqueue<Real>(c, o, seed, first, n, t, st, d);                                      \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_barrier_launch_##X(mc_context *c, const mc_barrier_##X *o, uint64_t seed, uint64_t first,\
+                                         uint64_t n, double *d_triple, void *stream)                         \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return barrier_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);       \
+    }                                                                                                        \
+    extern "C" int mc_barrier_run_##X(mc_context *c, const mc_barrier_##X *o, uint64_t seed, uint64_t first, \
+                                      uint64_t n, mc_result *out)                                            \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->option.r * (double)o->option.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return barrier_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                              \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_barrier_paths_##X(mc_context *c, const mc_barrier_##X *o, uint64_t seed, uint64_t first,\
+                                        uint64_t n, Real *h_out)                                             \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return barrier_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_normals_##X(mc_context *c, uint64_t seed, uint32_t domain, uint64_t first_unit,        \

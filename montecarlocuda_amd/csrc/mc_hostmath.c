@@ -10,6 +10,7 @@
  *   mc_factor_from_cov_*     SURVEY 8f-2
  *   mc_basket_control_mean_* closed-form mean of the geometric-basket control variate
  *   mc_asian_control_mean_*  closed-form mean of the geometric-average control variate of the Asian call
+ *   mc_barrier_closed_form_* Reiner-Rubinstein price of the continuously monitored single-barrier call
  *   mc_last_error / mc_internal_fail   the per-thread error text of whichever library this object is linked into
  */
 #include <math.h>
@@ -67,21 +68,25 @@ void mc_shard_range(uint64_t total, int rank, int world, uint64_t *first, uint64
 #define X f32
 #define BASKET mc_basket_f32
 #define ASIAN mc_asian_f32
+#define BARRIER mc_barrier_f32
 #include "mc_hostmath_impl.h"
 #undef REAL
 #undef SQRT_R
 #undef X
 #undef BASKET
 #undef ASIAN
+#undef BARRIER
 
 #define REAL double
 #define SQRT_R sqrt
 #define X f64
 #define BASKET mc_basket_f64
 #define ASIAN mc_asian_f64
+#define BARRIER mc_barrier_f64
 #include "mc_hostmath_impl.h"
 #undef REAL
 #undef SQRT_R
 #undef X
 #undef BASKET
 #undef ASIAN
+#undef BARRIER

@@ -1,11 +1,15 @@
 /* mc_hostmath.h -- internal: what mc_api.hip / host_path.c take from mc_hostmath.c besides the public symbols. */
 #ifndef MC_HOSTMATH_H_
 #define MC_HOSTMATH_H_
+#include "../../include/mc_mi355x.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
 /* Records the calling thread's error text (mc_last_error) and returns `code`. */
 int mc_internal_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+/* The input checks of the barrier call, shared by mc_barrier_closed_form_* and the GPU entry points (not exported). */
+int mc_barrier_check_f32(const mc_barrier_f32 *o, int need_vol);
+int mc_barrier_check_f64(const mc_barrier_f64 *o, int need_vol);
 #ifdef __cplusplus
 }
 #endif

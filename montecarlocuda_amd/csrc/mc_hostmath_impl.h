@@ -124,3 +124,59 @@ int FN(mc_asian_control_mean)(const ASIAN *o, double *mean)
     *mean = exp(mu + 0.5 * var) * 0.5 * erfc(-d1 / sqrt(2.0)) - k * 0.5 * erfc(-d2 / sqrt(2.0));
     return MC_OK;
 }
+
+/* The inputs every barrier entry point refuses (see mc_mi355x.h); need_vol: the forms that divide by v.  Internal
+ * (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_barrier_check)(const BARRIER *o, int need_vol)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    const double b = (double)o->barrier;
+    if (o->n_dates < 1 || o->n_dates > MC_MAX_BARRIER_DATES)
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: n_dates=%d outside [1, %d]", o->n_dates, MC_MAX_BARRIER_DATES);
+    if (o->type < MC_BARRIER_UP_OUT || o->type > MC_BARRIER_DOWN_IN)
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: type=%d is none of MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN", o->type);
+    if (o->monitoring != MC_MONITOR_DISCRETE && o->monitoring != MC_MONITOR_CONTINUOUS)
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: monitoring=%d is neither MC_MONITOR_DISCRETE nor MC_MONITOR_CONTINUOUS", o->monitoring);
+    if (!(s > 0) || !(t > 0) || !(b > 0) || !(v >= 0) || !isfinite(s) || !isfinite(t) || !isfinite(b) || !isfinite(r) || !isfinite(v) || !isfinite(k))
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: need s>0, t>0, barrier>0, v>=0 and finite inputs");
+    if (o->type <= MC_BARRIER_UP_IN ? s >= b : s <= b)
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: the spot %g is on or beyond the %s barrier %g: the product is then the vanilla call or nothing",
+                                s, o->type <= MC_BARRIER_UP_IN ? "up" : "down", b);
+    if (need_vol && !(v > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "barrier: continuous monitoring needs v != 0");
+    return MC_OK;
+}
+
+/* Discounted Reiner-Rubinstein price of the continuously monitored single-barrier call, no dividend, no rebate (Haug's
+ * terms A, B, C, D with phi = 1 and eta = +1 for a down, -1 for an up barrier), fp64, Phi by erfc. */
+int FN(mc_barrier_closed_form)(const BARRIER *o, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "barrier closed form: NULL argument");
+    int rc = FN(mc_barrier_check)(o, 1);
+    if (rc != MC_OK)
+        return rc;
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    const double b = (double)o->barrier;
+    if (!(k > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "barrier closed form: needs k > 0");
+    const int up = o->type <= MC_BARRIER_UP_IN, in = o->type == MC_BARRIER_UP_IN || o->type == MC_BARRIER_DOWN_IN;
+    const double eta = up ? -1.0 : 1.0;
+    const double sd = v * sqrt(t), mu = (r - 0.5 * v * v) / (v * v), shift = (1.0 + mu) * sd, kd = k * exp(-r * t);
+    const double x1 = log(s / k) / sd + shift, x2 = log(s / b) / sd + shift;
+    const double y1 = log(b * b / (s * k)) / sd + shift, y2 = log(b / s) / sd + shift;
+    const double pw = exp(2.0 * mu * log(b / s)), pw1 = pw * (b / s) * (b / s);   /* (B/S)^(2 mu), (B/S)^(2 mu + 2) */
+#define MC_PHI(x) (0.5 * erfc(-(x) / sqrt(2.0)))
+    const double A = s * MC_PHI(x1) - kd * MC_PHI(x1 - sd);
+    const double B = s * MC_PHI(x2) - kd * MC_PHI(x2 - sd);
+    const double Cc = s * pw1 * MC_PHI(eta * y1) - kd * pw * MC_PHI(eta * (y1 - sd));
+    const double D = s * pw1 * MC_PHI(eta * y2) - kd * pw * MC_PHI(eta * (y2 - sd));
+#undef MC_PHI
+    double in_price;   /* the knock-in call; the knock-out call is the vanilla call A minus it */
+    if (up)
+        in_price = k >= b ? A : B - Cc + D;
+    else
+        in_price = k >= b ? Cc : A - B + D;
+    *price = in ? in_price : A - in_price;
+    return MC_OK;
+}

@@ -1977,6 +1977,208 @@ __global__ __launch_bounds__(GROUP) void asian_kernel(const Tail /* first argume
 }
 
 // =========================================================================================
+// Single-barrier call on m equally spaced dates, monitored on the dates (CONT = false) or continuously through the
+// Brownian-bridge survival probability between them (CONT = true).  Not in the reference.  The walk is asian_path's, but in
+// LOG space: the lane's state is W_j and the running minimum of the distance to the barrier
+//   d_j = sgn (ln B - ln S_j) = fma(W_j, dbx, dk_j),   dbx = -sgn bx,   dk_j = sgn (ln B - ln S0 - j a)
+// (natural-log units; dk_j from the per-date table, folded in fp64 and rounded once -- small exactly where the path is near
+// the barrier, so d_j is well conditioned there; wave-uniform j: scalar loads, the fma's one scalar operand).  The direction
+// lives in the table and in the sign of dbx: up and down barriers run the same code.  Per path:
+//   discrete:    P = [min_j d_j > 0]                                             no transcendental in the date loop
+//   continuous:  P = [min_j d_j > 0] prod_j (1 - E(cexp d_{j-1} d_j)),  cexp = -2 / bx^2 (times log2 e in f32), d_0 from the host:
+//                one exponential per date.  On a crossed interval d_{j-1} d_j < 0 and the exponential may overflow; P is taken by
+//                a SELECT on min d_j > 0, never by a multiply, so inf and NaN stay out and a crossed path has P = 0 exactly
+//   value = (c0 + c1 P) (S_T - K)^+,  S_T = E(xT + bxe W_m): (c0, c1) = (0, 1) knock-out, (1, -1) knock-in, wave-uniform
+//   ANTI: the same at -z (d^-_j = fma(W_j, -dbx, dk_j)), value = mean of the two
+// Stream: domain 5, date j (0-based here) = entry j % NPB of block j / NPB: the Asian layout.
+// =========================================================================================
+template <class Real>
+struct BarrierArgs {
+    const Real *dk;   // n_dates values: sgn (ln B - ln S0 - (j + 1) a), natural-log units
+    int n_dates;
+    Real dbx;         // -sgn v sqrt(dt), natural-log units
+    Real d0;          // sgn (ln B - ln S0) > 0: the distance at t_0, where the first bridge starts
+    Real cexp;        // -2 / bx^2 in the exponential's units (f32: times log2 e, so the product goes straight into v_exp_f32)
+    Real xT, bxe;     // ln S_T = xT + bxe W_m in exponent units (natural log in f64, log2 in f32)
+    Real strike;
+    Real c0, c1;      // value = (c0 + c1 P) payoff
+};
+
+// the survival factor of the running distances is folded by barrier_value: P, then the payoff at maturity
+template <bool CONT, class Real>
+__device__ __forceinline__ Real barrier_value(Real mn, Real prod, Real W, const BarrierArgs<Real> &o)
+{
+    const Real live = CONT ? prod : (Real)1;
+    const Real P = mn > 0 ? live : (Real)0;   // the select: a NaN or inf product of a crossed path never reaches the value
+    const Real pay = exp_model(fma_r(W, o.bxe, o.xT)) - o.strike;
+    return fma_r(o.c1, P, o.c0) * (pay > 0 ? pay : 0);
+}
+
+// fp32: a block of four normals = two packed date pairs per trip, as asian_path<float>: Wp = {W + z0, W + z0 + z1}, one
+// v_pk_fma_f32 for the pair's distances (its addend the pair's {dk, dk'} from two adjacent SGPRs), one v_min3_f32 for the
+// running minimum (gfx950 has no packed fp32 min).  CONT adds per pair: one packed multiply by cexp, one packed multiply
+// by the previous distances, two v_exp_f32 and one packed fma prod (1 - e) into the even / odd halves of the product.
+template <bool ANTI, bool CONT, class Gen>
+__device__ __forceinline__ float barrier_path(Gen &gen, const BarrierArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two packed date pairs per block");
+    const int n = o.n_dates;
+    // dbx in a vector register pair for the whole path: the packed fma's ONE scalar operand is the pair's {dk, dk'}
+    f2 dbx = bcast(o.dbx);
+    asm("" : "+v"(dbx));
+    const f2 one = bcast(1.0f);
+    [[maybe_unused]] const f2 cexp = bcast(o.cexp);
+    float W = 0, mn = __builtin_inff(), mn_m = __builtin_inff();
+    float tp = o.cexp * o.d0, tp_m = tp;              // cexp d_{j-1} of the last date seen
+    f2 prod = one, prod_m = one;                      // even / odd dates
+    float z[NPB];
+    auto side = [&](f2 d, float &mn_, float &tp_, f2 &prod_) {
+        mn_ = __builtin_fminf(__builtin_fminf(mn_, d.x), d.y);
+        if (CONT) {
+            const f2 t = d * cexp;
+            const f2 u = (f2){tp_, t.x} * d;
+            prod_ = pk_fma(-prod_, pk_exp2(u), prod_);   // prod (1 - e)
+            tp_ = t.y;
+        }
+    };
+    auto pair = [&](int j, float z0, float z1) {
+        const f2 Wp = {W + z0, (W + z0) + z1};
+        W = Wp.y;
+        const f2 dk = {o.dk[j], o.dk[j + 1]};
+        side(pk_fma(Wp, dbx, dk), mn, tp, prod);
+        if (ANTI)
+            side(pk_fma(-Wp, dbx, dk), mn_m, tp_m, prod_m);
+    };
+    auto single = [&](float d, float &mn_, float &tp_, f2 &prod_) {
+        mn_ = __builtin_fminf(mn_, d);
+        if (CONT) {
+            prod_.x = __builtin_fmaf(-prod_.x, __builtin_amdgcn_exp2f(tp_ * d), prod_.x);
+            tp_ = o.cexp * d;
+        }
+    };
+    int j0 = 0;
+    for (; j0 + NPB <= n; j0 += NPB) {
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 5u /*MC_DOMAIN_BARRIER*/, z);
+        pair(j0, z[0], z[1]);
+        pair(j0 + 2, z[2], z[3]);
+    }
+    if (j0 < n) {   // wave-uniform: one to three dates left
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 5u /*MC_DOMAIN_BARRIER*/, z);
+        if (j0 + 2 <= n) {
+            pair(j0, z[0], z[1]);
+            j0 += 2;
+        }
+        if (j0 < n) {
+            W += j0 & 2 ? z[2] : z[0];
+            const float dk = o.dk[j0];
+            single(__builtin_fmaf(W, o.dbx, dk), mn, tp, prod);
+            if (ANTI)
+                single(__builtin_fmaf(-W, o.dbx, dk), mn_m, tp_m, prod_m);
+        }
+    }
+    float val = barrier_value<CONT>(mn, prod.x * prod.y, W, o);
+    if (ANTI)
+        val = 0.5f * (val + barrier_value<CONT>(mn_m, prod_m.x * prod_m.y, -W, o));
+    return val;
+}
+
+// min(a, b) of two doubles that are never signalling NaNs, as ONE v_min_f64 (hipcc puts a canonicalising v_max_f64 in front of the
+// running minimum's __builtin_fmin on every date)
+__device__ __forceinline__ double min_f64(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// fp64: asian_path<double>'s loop (Box-Muller pairs through the generator's pair cursor, four pairs per trip, then one): per
+// date one add, one v_fma_f64 with dk_j from its SGPR pair and one v_min_f64.  CONT: the exponent is clamped from below
+// (exp_f64's argument range; a live path's exponent is negative and e^-800 is 0 anyway), what a crossed interval gives is dropped
+// by the select.
+template <bool ANTI, bool CONT, class Gen>
+__device__ __forceinline__ double barrier_path(Gen &gen, const BarrierArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.n_dates;
+    double W = 0, mn = __builtin_inf(), mn_m = __builtin_inf(), prod = 1.0, prod_m = 1.0;
+    double tp = o.cexp * o.d0, tp_m = tp;
+    const double dbx_v = to_vgpr(o.dbx);
+    [[maybe_unused]] const double ndbx_v = to_vgpr(-o.dbx);
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto side = [&](double d, double &mn_, double &tp_, double &prod_) {
+        mn_ = min_f64(mn_, d);
+        if (CONT) {
+            const double u = __builtin_fmax(tp_ * d, -800.0);
+            prod_ = __builtin_fma(-prod_, exp_f64(u), prod_);
+            tp_ = o.cexp * d;
+        }
+    };
+    auto date = [&](int j, double z) {
+        W += z;
+        const double dk = o.dk[j];
+        side(fma_scalar_addend(W, dbx_v, dk), mn, tp, prod);
+        if (ANTI)
+            side(fma_scalar_addend(W, ndbx_v, dk), mn_m, tp_m, prod_m);
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 8 <= n; j += 8) {
+            uint32_t blk = (uint32_t)(j >> 3);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // discrete form: a pair's generator call starts after the running minimum of the pair before it (its block index
+                // passes through the same empty statement).  Left free, hipcc overlaps the four calls around the few
+                // instructions of the dates and needs 129 vector registers: three waves per SIMD instead of four.  (A scheduling
+                // barrier does the same but counts as a memory write, which turns the table's scalar loads into vector loads.)
+                if (!CONT && k)
+                    asm("" : "+v"(mn), "+s"(blk));
+                double z0, z1;
+                gen.pair(w, c0, 5u /*MC_DOMAIN_BARRIER*/, (blk << 2) | k, carry, z0, z1);
+                date(j + 2 * (int)k, z0);
+                date(j + 2 * (int)k + 1, z1);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; j += 2) {
+        double z0, z1;
+        gen.pair(w, c0, 5u /*MC_DOMAIN_BARRIER*/, (uint32_t)(j >> 1), carry, z0, z1);
+        date(j, z0);
+        if (j + 1 < n)   // wave-uniform
+            date(j + 1, z1);
+    }
+    gen.pairs_done((uint32_t)((n + 1) >> 1));
+    double val = barrier_value<CONT>(mn, prod, W, o);
+    if (ANTI)
+        val = 0.5 * (val + barrier_value<CONT>(mn_m, prod_m, -W, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths.  Four waves per SIMD at least, asian_kernel's occupancy in fp64: left to
+// itself hipcc spends 129 vector registers on the fp64 discrete forms (one more than four waves allow) on a loop that needs fewer.
+template <class Real, bool ANTI, bool CONT, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void barrier_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const BarrierArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = barrier_path<ANTI, CONT>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // CVA, parallel in the DATE axis.  Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
 // its path.  With the reformulation above the lane's only state is W_j = z_1 + ... + z_j and everything else is a table
 // row of the date, so the walk is a prefix sum followed by independent work: here a path's dates are shared by

@@ -109,6 +109,18 @@ def _as_asian(X, a, n_dates=None) -> C.Structure:
     return _lib.ASIAN[X](_as_option(X, a), int(n_dates))
 
 
+def _as_barrier(X, o, barrier=None, n_dates=None, kind=None, monitoring=None) -> C.Structure:
+    """mc_barrier_*: an option (OptionData or dict) with the barrier's fields, or a dict that carries "barrier", "n_dates" and
+    optionally "kind" / "monitoring" itself.  kind and monitoring: the names of _lib.BARRIER_TYPES / _lib.MONITORING, or the
+    header's integers."""
+    if barrier is None:
+        barrier, n_dates = o["barrier"], o["n_dates"]
+        kind, monitoring = o.get("kind", "up-and-out"), o.get("monitoring", "discrete")
+    kind = _lib.BARRIER_TYPES[kind] if isinstance(kind, str) else int(kind)
+    monitoring = _lib.MONITORING[monitoring] if isinstance(monitoring, str) else int(monitoring)
+    return _lib.BARRIER[X](_as_option(X, o), float(barrier), int(n_dates), kind, monitoring)
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -354,6 +366,13 @@ class Engine:
         set_control_variate (the geometric-average control's closed-form mean is added back)."""
         return self._run("asian", precision, _as_asian(precision, opt, n_dates), seed, first_path, n_paths)
 
+    def barrier(self, opt, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out",
+                monitoring="discrete") -> Estimate:
+        """Single-barrier call on n_dates equally spaced dates (mc_barrier_run_*).  kind: "up-and-out", "up-and-in", "down-and-out",
+        "down-and-in"; monitoring: "discrete" (on the dates only) or "continuous" (Brownian-bridge survival probability between
+        the dates: unbiased for the continuously monitored price, barrier_closed_form).  Honours set_antithetic."""
+        return self._run("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
@@ -371,6 +390,8 @@ class Engine:
             return h.struct, h
         if prod == "asian":   # inputs: the option's fields plus "n_dates"
             return _as_asian(precision, inputs), None
+        if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
+            return _as_barrier(precision, inputs), None
         return _as_cva(precision, inputs), None
 
     # ---- per-path values (parity tests) ------------------------------------------------
@@ -392,6 +413,10 @@ class Engine:
 
     def asian_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("asian", precision, _as_asian(precision, opt, n_dates), seed, first_path, n_paths)
+
+    def barrier_paths(self, opt, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out",
+                      monitoring="discrete"):
+        return self._paths("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
 
     def normals(self, seed, domain, first_unit, n_units, block=0, precision="f64"):
         npb = 4 if (precision == "f32" or self._normals_f32) else 8
@@ -494,6 +519,13 @@ def asian_control_mean(opt, n_dates, precision="f64"):
     m = C.c_double()
     check(getattr(lib(), f"mc_asian_control_mean_{precision}")(C.byref(_as_asian(precision, opt, n_dates)), C.byref(m)))
     return m.value
+
+
+def barrier_closed_form(opt, barrier, kind="up-and-out", precision="f64"):
+    """Discounted Reiner-Rubinstein price of the continuously monitored single-barrier call (no dividend, no rebate; fp64)."""
+    p = C.c_double()
+    check(getattr(lib(), f"mc_barrier_closed_form_{precision}")(C.byref(_as_barrier(precision, opt, barrier, 1, kind, "continuous")), C.byref(p)))
+    return p.value
 
 
 def chol(c, precision="f64"):
