@@ -69,6 +69,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_CVA 3u
 #define MC_DOMAIN_ASIAN 4u
 #define MC_DOMAIN_BARRIER 5u
+#define MC_DOMAIN_HESTON 6u
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -112,6 +113,14 @@ enum { MC_BARRIER_UP_OUT = 0, MC_BARRIER_UP_IN = 1, MC_BARRIER_DOWN_OUT = 2, MC_
 enum { MC_MONITOR_DISCRETE = 0, MC_MONITOR_CONTINUOUS = 1 };
 typedef struct { mc_option_f32 option; float barrier; int n_dates, type, monitoring; } mc_barrier_f32;
 typedef struct { mc_option_f64 option; double barrier; int n_dates, type, monitoring; } mc_barrier_f64;
+
+/* European call under the Heston stochastic-volatility model, full-truncation Euler on n_steps equal steps (see
+ * mc_heston_run_*).  Not in the reference.  option.v is ignored: the variance starts at v0.  No constant table: every per-step
+ * constant is a kernel argument.  The cap keeps the fp32 running sums over the steps at the Asian call's worst-case
+ * rounding (~ n_steps 2^-24 relative). */
+#define MC_MAX_HESTON_STEPS 4096
+typedef struct { mc_option_f32 option; float v0, kappa, theta, xi, rho; int n_steps; } mc_heston_f32;
+typedef struct { mc_option_f64 option; double v0, kappa, theta, xi, rho; int n_steps; } mc_heston_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -369,6 +378,48 @@ int mc_barrier_paths_f32(mc_context *ctx, const mc_barrier_f32 *opt, uint64_t se
 int mc_barrier_paths_f64(mc_context *ctx, const mc_barrier_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 int mc_barrier_closed_form_f32(const mc_barrier_f32 *opt, double *price);
 int mc_barrier_closed_form_f64(const mc_barrier_f64 *opt, double *price);
+
+/* ---- European call under the Heston model: full-truncation Euler in log space -----------------------------
+ * dS = r S dt + sqrt(V) S dW1,  dV = kappa (theta - V) dt + xi sqrt(V) dW2,  corr(dW1, dW2) = rho,  V(0) = v0.
+ * On m = n_steps equal steps: dt = t/m, sdt = sqrt(dt), rho' = sqrt(1 - rho^2), x_0 = ln s, V_0 = v0, and for j = 1 ... m,
+ * with the step's two normals (z1_j, z2_j):
+ *     V+  = max(V_{j-1}, 0)        s = sqrt(V+)
+ *     x_j = x_{j-1} + (r - V+/2) dt + s sdt z1_j
+ *     V_j = V_{j-1} + kappa (theta - V+) dt + xi sdt s (rho z1_j + rho' z2_j)
+ * Per path, undiscounted, the value is (exp(x_m) - k)^+.  mc_context_set_antithetic: the mean of the value at (z1, z2) and at
+ * (-z1, -z2), each with its own V; n counts pairs.  xi = 0, kappa = 0, |rho| = 1 and a violated Feller condition
+ * (2 kappa theta < xi^2) are valid inputs.  option.v is ignored.
+ * Stream: path p is unit p of MC_DOMAIN_HESTON; step j (1-based) draws entries 2(j-1) % npb and 2(j-1) % npb + 1 of block
+ * 2(j-1) / npb as z1 and z2 (npb = 4 in f32, 8 in f64): the Asian layout with two entries per step; in f64 that is pair
+ * (j-1) of the generator's Box-Muller pairs.  A path's value depends on (seed, global path index, inputs) only.
+ * Path ranges, the finish, call statistics, timing, arming and ordering as for the other products; several GPUs:
+ * mc_heston_launch_* on the ranges of mc_shard_range, the triples added, mc_closing.
+ * MC_ERR_INVALID before anything is enqueued: n_steps outside [1, MC_MAX_HESTON_STEPS]; s <= 0, t <= 0, v0 < 0, kappa < 0,
+ * theta < 0, xi < 0, |rho| > 1; a non-finite input; inputs whose scale of drift and volatility over the m steps is beyond the
+ * argument range of the device's exponential (a heuristic guard against absurd inputs, not a bound on the variance); the range
+ * errors of the other products.  MC_ERR_UNSUPPORTED: the control
+ * variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a context set up for external
+ * normals or the launch geometry.  The context stays usable.  No puts, Greeks, book, other discretisation schemes or
+ * path-dependent payoffs.  mc_heston_paths_* returns the per-path values (undiscounted; n_paths <= 2^26).
+ * mc_heston_closed_form_*: the exact price of the call in the CONTINUOUS model (discounted, no dividend) -- not of the Euler
+ * scheme, whose bias shrinks with dt.  Heston's P1 / P2 decomposition with the branch-cut-safe ("little Heston trap")
+ * characteristic function, integrated in fp64 by 16-point Gauss-Legendre on panels of the fixed width 1 / (4 sd), sd^2 = t times
+ * the mean variance over [0, t], until both integrands have stayed below 1e-18 for a whole panel; xi == 0 is Black-Scholes at
+ * that mean variance.  Ignores n_steps; usable without a GPU; the input checks above, and k > 0.
+ * MC_ERR_INVALID too when the integrands have not decayed within 40000 panels (|rho| = 1 with a tiny variance).
+ * Verified: within 1e-11 absolute at s = 100 (measured: 3.6e-13) of an independent quadrature of Lewis's single integral over
+ * the cases and strikes of tests/test_heston_ref.py, kappa = 0 and |rho| = 1 included; for 0 < xi << 1 the cancellation in
+ * beta - d costs about 1e-16 kappa theta / xi^2 relative (checked to 1e-9 at xi = 1e-3); 6.8061 on the case of Broadie and Kaya. */
+int mc_heston_run_f32(mc_context *ctx, const mc_heston_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_run_f64(mc_context *ctx, const mc_heston_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_launch_f32(mc_context *ctx, const mc_heston_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                         double *d_triple, void *stream);
+int mc_heston_launch_f64(mc_context *ctx, const mc_heston_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                         double *d_triple, void *stream);
+int mc_heston_paths_f32(mc_context *ctx, const mc_heston_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_heston_paths_f64(mc_context *ctx, const mc_heston_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_heston_closed_form_f32(const mc_heston_f32 *opt, double *price);
+int mc_heston_closed_form_f64(const mc_heston_f64 *opt, double *price);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

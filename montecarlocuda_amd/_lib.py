@@ -15,9 +15,10 @@ LEGACY = {"f64": os.path.join(CSRC, "libmcgpu_f64.so"), "f32": os.path.join(CSRC
 
 MC_OK = 0
 MC_DEFAULT_SEED = 0x4D435F4D49333535
-DOMAIN_VANILLA, DOMAIN_BASKET, DOMAIN_CVA, DOMAIN_ASIAN, DOMAIN_BARRIER = 1, 2, 3, 4, 5
+DOMAIN_VANILLA, DOMAIN_BASKET, DOMAIN_CVA, DOMAIN_ASIAN, DOMAIN_BARRIER, DOMAIN_HESTON = 1, 2, 3, 4, 5, 6
 MAX_ASIAN_DATES = 4096   # MC_MAX_ASIAN_DATES
 MAX_BARRIER_DATES = 4096   # MC_MAX_BARRIER_DATES
+MAX_HESTON_STEPS = 4096   # MC_MAX_HESTON_STEPS
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
 MAX_ASSETS = 16          # register-resident basket kernels
@@ -76,6 +77,16 @@ class BarrierF64(C.Structure):   # mc_barrier_f64
     _fields_ = [("option", OptionF64), ("barrier", C.c_double), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
 
 
+class HestonF32(C.Structure):   # mc_heston_f32
+    _fields_ = [("option", OptionF32), ("v0", C.c_float), ("kappa", C.c_float), ("theta", C.c_float), ("xi", C.c_float), ("rho", C.c_float),
+                ("n_steps", C.c_int)]
+
+
+class HestonF64(C.Structure):   # mc_heston_f64
+    _fields_ = [("option", OptionF64), ("v0", C.c_double), ("kappa", C.c_double), ("theta", C.c_double), ("xi", C.c_double), ("rho", C.c_double),
+                ("n_steps", C.c_int)]
+
+
 class Result(C.Structure):
     _fields_ = [("expected", C.c_double), ("confidence", C.c_double), ("sum", C.c_double), ("sum2", C.c_double),
                 ("n", C.c_uint64), ("kernel_ms", C.c_float), ("wall_ms", C.c_float)]
@@ -113,6 +124,7 @@ BASKET = {"f32": BasketF32, "f64": BasketF64}
 CVA = {"f32": CvaF32, "f64": CvaF64}
 ASIAN = {"f32": AsianF32, "f64": AsianF64}
 BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
+HESTON = {"f32": HestonF32, "f64": HestonF64}
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -133,6 +145,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_vanilla_book_run_{_x}", f"mc_vanilla_book_launch_{_x}"]
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
+    EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -213,6 +226,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_barrier_run_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_barrier_paths_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, RP]
         getattr(L, f"mc_barrier_closed_form_{X}").argtypes = [C.POINTER(BARRIER[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_heston_launch_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), C.POINTER(C.c_double)]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

@@ -363,12 +363,12 @@ extern "C" int mc_context_describe(const mc_context *c, char *buf, int len)
     snprintf(buf, (size_t)len,
              "mc_context config: device=%d \"%s\" CUs=%d clock_mhz=%d blocks=%d finish=%s f64_normals=%s rng=%s antithetic=%d control_variate=%d timing=%d "
              "grid_form=%s basket_static_max=f32:%d,f64:%d basket_tiled_min=%d basket_mfma=%d grid_sub=%d(0=auto) vanilla_units_per_lane=%d cva_date_lanes=%d(0=auto) "
-             "asian_dates_max=%d barrier_dates_max=%d created_in_ms=%.1f",
+             "asian_dates_max=%d barrier_dates_max=%d heston_steps_max=%d created_in_ms=%.1f",
              c->device, c->name, c->compute_units, c->clock_mhz, c->blocks, c->fused ? "fused" : "kernel", c->normals_f32 ? "f32" : "native",
              c->rng == MC_RNG_XORWOW ? "xorwow" : "philox", (int)c->antithetic, (int)c->control, (int)c->timing,
              c->grid_form == MC_GRID_FORM_STAGED ? "staged" : (c->grid_form == MC_GRID_FORM_FUSED ? "fused" : "auto"), basket_static_max<float>(),
              basket_static_max<double>(), basket_tiled_min(), (int)basket_mfma(), env_int("MC_GRID_SUB", 0, 0, 32), vanilla_units_per_lane(), c->cva_date_lanes,
-             MC_MAX_ASIAN_DATES, MC_MAX_BARRIER_DATES, c->create_ms);
+             MC_MAX_ASIAN_DATES, MC_MAX_BARRIER_DATES, MC_MAX_HESTON_STEPS, c->create_ms);
     return MC_OK;
 }
 
@@ -2304,6 +2304,75 @@ static int barrier_enqueue(mc_context *c, const typename BarrierIn<Real>::type *
 }
 
 // ---------------------------------------------------------------------------------------
+// European call under the Heston model (full-truncation Euler): heston_kernel, one lane per path, no table
+// ---------------------------------------------------------------------------------------
+template <class Real> struct HestonIn;
+template <> struct HestonIn<float> { using type = mc_heston_f32; };
+template <> struct HestonIn<double> { using type = mc_heston_f64; };
+static int heston_check(const mc_heston_f32 &o) { return mc_heston_check_f32(&o); }
+static int heston_check(const mc_heston_f64 &o) { return mc_heston_check_f64(&o); }
+
+// The per-step constants, folded in fp64 and rounded once.  The maturity exponent x_m = x0 + av sum V+ + aw sum s z1 is in the
+// exponential's units (fp32: times log2 e, so it goes straight into v_exp_f32).
+template <class Real>
+static int heston_args(const typename HestonIn<Real>::type *v, HestonArgs<Real> &args)
+{
+    const auto &o = v->option;
+    const double sc = exp_scale<Real>();
+    const double m = (double)v->n_steps, dt = (double)o.t / m, sdt = std::sqrt(dt), ln_s0 = std::log((double)o.s);
+    const double kappa = (double)v->kappa, theta = (double)v->theta, xi = (double)v->xi, rho = (double)v->rho;
+    // as for the Asian call, only the hard limit of the device's exp is aimed at, and here by a HEURISTIC: vb is a scale of the
+    // variance (its start, its mean level and the square of what the noise adds over the whole life), not an upper bound on it --
+    // sqrt(V) can grow by xi sdt Zmax / 2 on every step.  It refuses absurd inputs early; beyond exp_f64's argument range the
+    // value of a path is garbage, never a fault, and below it an honest overflow gives inf
+    const double vb = (double)v->v0 + theta + xi * xi * (double)o.t * Z_MAX_F64 * Z_MAX_F64;
+    if (!(std::fabs(ln_s0) + std::fabs((double)o.r) * (double)o.t + m * (0.5 * vb * dt + std::sqrt(vb) * sdt * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+        return fail(MC_ERR_INVALID, "heston: drift and volatility put the simulated spot outside the range of a double");
+    args.n_steps = v->n_steps;
+    args.v0 = v->v0;
+    args.kdt = (Real)(kappa * dt);
+    args.ktdt = (Real)(kappa * theta * dt);
+    args.c1 = (Real)(xi * sdt * rho);
+    args.c2 = (Real)(xi * sdt * std::sqrt(1.0 - rho * rho));
+    args.x0 = (Real)((ln_s0 + (double)o.r * (double)o.t) * sc);
+    args.av = (Real)(-0.5 * dt * sc);
+    args.aw = (Real)(sdt * sc);
+    args.strike = o.k;
+    return MC_OK;
+}
+
+template <class Real>
+static int heston_enqueue(mc_context *c, const typename HestonIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                          double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "heston: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "heston: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "heston: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_UNSUPPORTED, "heston: no control variate");
+    if (int rc = heston_check(*v)) return rc;
+    HestonArgs<Real> args;
+    if (int rc = heston_args<Real>(v, args)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) launch_sim(prof, heston_kernel<Real, true>, g, st, t, args, w, dst);
+            else               launch_sim(prof, heston_kernel<Real, false>, g, st, t, args, w, dst);
+            return MC_OK;
+        });
+}
+
+// ---------------------------------------------------------------------------------------
 // Greeks of the basket call and of the CVA: secondary kernels, plain estimator, synchronous
 // ---------------------------------------------------------------------------------------
 // the inputs' checks and the constant table of basket_greeks_kernel (and, LR = true, of basket_gamma_kernel), uploaded
@@ -3136,6 +3205,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return barrier_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_heston_launch_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first,\
+                                        uint64_t n, double *d_triple, void *stream)                          \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return heston_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);        \
+    }                                                                                                        \
+    extern "C" int mc_heston_run_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first,   \
+                                     uint64_t n, mc_result *out)                                             \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->option.r * (double)o->option.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return heston_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                               \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_heston_paths_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first, \
+                                       uint64_t n, Real *h_out)                                              \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return heston_enqueue<Real>(c, o, seed, first, n, t, st, d);                                     \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_normals_##X(mc_context *c, uint64_t seed, uint32_t domain, uint64_t first_unit,        \

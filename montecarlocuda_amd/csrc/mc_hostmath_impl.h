@@ -180,3 +180,50 @@ int FN(mc_barrier_closed_form)(const BARRIER *o, double *price)
     *price = in ? in_price : A - in_price;
     return MC_OK;
 }
+
+/* The inputs every Heston entry point refuses (see mc_mi355x.h).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_heston_check)(const HESTON *o)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, t = (double)o->option.t;
+    const double v0 = (double)o->v0, kappa = (double)o->kappa, theta = (double)o->theta, xi = (double)o->xi, rho = (double)o->rho;
+    if (o->n_steps < 1 || o->n_steps > MC_MAX_HESTON_STEPS)
+        return mc_internal_fail(MC_ERR_INVALID, "heston: n_steps=%d outside [1, %d]", o->n_steps, MC_MAX_HESTON_STEPS);
+    if (!isfinite(s) || !isfinite(k) || !isfinite(r) || !isfinite(t) || !isfinite(v0) || !isfinite(kappa) || !isfinite(theta) || !isfinite(xi) ||
+        !isfinite(rho))
+        return mc_internal_fail(MC_ERR_INVALID, "heston: need finite s, k, r, t, v0, kappa, theta, xi, rho");
+    if (!(s > 0) || !(t > 0) || !(v0 >= 0) || !(kappa >= 0) || !(theta >= 0) || !(xi >= 0) || !(fabs(rho) <= 1))
+        return mc_internal_fail(MC_ERR_INVALID, "heston: need s>0, t>0, v0>=0, kappa>=0, theta>=0, xi>=0, |rho|<=1");
+    return MC_OK;
+}
+
+/* Discounted exact price of the European call under the Heston model (see mc_mi355x.h and heston_call_fp64).  xi == 0 leaves a
+ * deterministic variance: Black-Scholes at the mean variance over [0, t] (the discounted intrinsic value where that is 0). */
+int FN(mc_heston_closed_form)(const HESTON *o, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "heston closed form: NULL argument");
+    HESTON one = *o;
+    one.n_steps = 1;   /* ignored here */
+    int rc = FN(mc_heston_check)(&one);
+    if (rc != MC_OK)
+        return rc;
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, t = (double)o->option.t;
+    const double v0 = (double)o->v0, kappa = (double)o->kappa, theta = (double)o->theta, xi = (double)o->xi, rho = (double)o->rho;
+    if (!(k > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "heston closed form: needs k > 0");
+    if (xi == 0 || (v0 == 0 && kappa * theta == 0)) {   /* the second: the variance never leaves 0 */
+        const double kt = kappa * t, w = kt > 0 ? theta + (v0 - theta) * (-expm1(-kt)) / kt : v0, sd = sqrt(w * t), kd = k * exp(-r * t);
+        if (!(sd > 0)) {
+            *price = fmax(s - kd, 0.0);
+            return MC_OK;
+        }
+        const double d1 = (log(s / k) + r * t) / sd + 0.5 * sd;
+        *price = s * 0.5 * erfc(-d1 / sqrt(2.0)) - kd * 0.5 * erfc(-(d1 - sd) / sqrt(2.0));
+        return MC_OK;
+    }
+    const double c = heston_call_fp64(s, k, r, t, v0, kappa, theta, xi, rho);
+    if (!isfinite(c))
+        return mc_internal_fail(MC_ERR_INVALID, "heston closed form: the integrand does not decay within the quadrature's 40000 panels for these inputs");
+    *price = c;
+    return MC_OK;
+}

@@ -2179,6 +2179,183 @@ __global__ __launch_bounds__(GROUP) void barrier_kernel(const Tail /* first argu
 }
 
 // =========================================================================================
+// European call under the Heston stochastic-volatility model, full-truncation Euler in log space on m equal steps (the model
+// is stated in mc_mi355x.h).  Not in the reference.  The first walk here whose step is non-linear in its state: besides the
+// normals a lane carries the variance V and two running sums, because
+//   x_m = ln S0 + r T - (dt/2) sum_j V+_{j-1} + sdt sum_j s_{j-1} z1_j          (V+ = max(V, 0), s = sqrt(V+))
+// is the same real number as the step-by-step x_j and leaves two accumulations per step; the exponential is taken once, at
+// maturity.  Per step, with t = c1 z1 + c2 z2 (c1 = xi sdt rho, c2 = xi sdt rho'):
+//   V+ = max(V, 0);  s = sqrt(V+);  sv += V+;  sw = fma(s, z1, sw);  V = fma(s, t, fma(-kdt, V+, V + ktdt))
+// Every constant is a kernel argument, folded on the host in fp64 and rounded once: no table.
+//   ANTI: a second (V, sv, sw) walked on (-z1, -z2) -- nothing is shared but the normals and t -- value = mean of the two
+// sqrt(0) on a truncated step: fp32 takes v_sqrt_f32, which gives 0 exactly; fp64 takes sqrt_trunc below.
+// Stream: domain 6, step j (0-based here) = entries 2j % NPB, 2j % NPB + 1 of block 2j / NPB: fp32 two steps per Philox
+// block, fp64 pair j of the pair cursor.
+// =========================================================================================
+template <class Real>
+struct HestonArgs {
+    int n_steps;
+    Real v0;
+    Real kdt, ktdt;   // kappa dt, kappa theta dt
+    Real c1, c2;      // xi sqrt(dt) rho, xi sqrt(dt) sqrt(1 - rho^2)
+    Real x0, av, aw;  // x_m = x0 + av sum V+ + aw sum s z1 in exponent units (natural log in f64, log2 in f32): ln S0 + r T, -dt/2, sqrt(dt)
+    Real strike;
+};
+
+template <class Real>
+struct HestonSide {
+    Real V, sv, sw;   // the variance, sum V+, sum s z1
+};
+
+__device__ __forceinline__ float sqrt_trunc(float, float vp, float) { return __builtin_amdgcn_sqrtf(vp); }
+__device__ __forceinline__ float max0(float v) { return __builtin_fmaxf(v, 0.0f); }
+// max(a, 0) and max(a, b) of doubles that are never signalling NaNs as ONE v_max_f64 each (see min_f64)
+__device__ __forceinline__ double max0(double a)
+{
+    double r;
+    asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ double max_scalar_f64(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+    return r;
+}
+// sqrt(max(v, 0)) in fp64, vp = max(v, 0) given.  sqrt_pos (mc_math_f64.hpp) starts from v_rsq_f64 of the radicand, which is inf at
+// 0 and makes inf * 0 of a truncated step.  Here the reciprocal root is taken of max(v, floor), floor = 2^-1000, and multiplied
+// into vp: at vp = 0 every product below is an exact 0 next to finite factors and the result is exactly 0; for 0 < vp < floor
+// the Newton steps do not converge, but everything stays below 2^-498 and so does the error; from floor up it is sqrt_pos
+// instruction for instruction.  Cost: one v_max_f64 per root, no compare, no select.
+__device__ __forceinline__ double sqrt_trunc(double v, double vp, double floor)
+{
+    const double y = __builtin_amdgcn_rsq(max_scalar_f64(v, floor));
+    double g = vp * y;
+    double h = 0.5 * y;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    const double d = __builtin_fma(-g, g, vp);
+    return __builtin_fma(d, h, g);
+}
+
+template <class Real>
+__device__ __forceinline__ void heston_step(HestonSide<Real> &p, Real z1, Real t, const HestonArgs<Real> &o, Real floor)
+{
+    const Real vp = max0(p.V);
+    const Real s = sqrt_trunc(p.V, vp, floor);
+    p.sv += vp;
+    p.sw = fma_r(s, z1, p.sw);
+    p.V = fma_r(s, t, fma_r(-o.kdt, vp, p.V + o.ktdt));
+}
+
+template <class Real>
+__device__ __forceinline__ Real heston_value(const HestonSide<Real> &p, const HestonArgs<Real> &o)
+{
+    const Real pay = exp_model(fma_r(o.aw, p.sw, fma_r(o.av, p.sv, o.x0))) - o.strike;
+    return pay > 0 ? pay : 0;
+}
+
+// fp32: one Philox block of four normals = two steps per trip
+template <bool ANTI, class Gen>
+__device__ __forceinline__ float heston_path(Gen &gen, const HestonArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two steps per block");
+    const int n = o.n_steps;
+    HestonSide<float> p = {o.v0, 0.0f, 0.0f}, q = p;
+    float z[NPB];
+    auto step = [&](float z1, float z2) {
+        const float t = __builtin_fmaf(z2, o.c2, o.c1 * z1);
+        heston_step(p, z1, t, o, 0.0f);
+        if (ANTI)
+            heston_step(q, -z1, -t, o, 0.0f);
+    };
+    int j = 0;
+    for (; j + 2 <= n; j += 2) {
+        gen.normals(w, c0, (uint32_t)(j >> 1), 6u /*MC_DOMAIN_HESTON*/, z);
+        step(z[0], z[1]);
+        step(z[2], z[3]);
+    }
+    if (j < n) {   // wave-uniform: the odd last step
+        gen.normals(w, c0, (uint32_t)(j >> 1), 6u /*MC_DOMAIN_HESTON*/, z);
+        step(z[0], z[1]);
+    }
+    float val = heston_value(p, o);
+    if (ANTI)
+        val = 0.5f * (val + heston_value(q, o));
+    return val;
+}
+
+// fp64: one Box-Muller pair of the generator's pair cursor per step, four pairs per trip for the bulk (the cursor's phase a
+// compile-time constant in each copy), one pair per trip for the rest: asian_path<double>'s loop with a step where it has two dates.
+template <bool ANTI, class Gen>
+__device__ __forceinline__ double heston_path(Gen &gen, const HestonArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.n_steps;
+    HestonSide<double> p = {o.v0, 0.0, 0.0}, q = p;
+    const double floor = 0x1p-1000;
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto step = [&](double z1, double z2) {
+        const double t = __builtin_fma(z2, o.c2, o.c1 * z1);
+        heston_step(p, z1, t, o, floor);
+        if (ANTI)
+            heston_step(q, -z1, -t, o, floor);
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 4 <= n; j += 4) {
+            uint32_t g4 = (uint32_t)(j >> 2) << 2;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // a step's generator call starts after the variance of the step before it (its pair index passes through the same
+                // empty statement: barrier_path<double>'s tie).  Left free, hipcc overlaps the four calls of a trip around the few
+                // instructions of the steps and the antithetic form needs 132 vector registers: three waves per SIMD instead of four.
+                if (ANTI && k)
+                    asm("" : "+v"(p.V), "+s"(g4));
+                double z0, z1;
+                gen.pair(w, c0, 6u /*MC_DOMAIN_HESTON*/, g4 | k, carry, z0, z1);
+                step(z0, z1);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; ++j) {
+        double z0, z1;
+        gen.pair(w, c0, 6u /*MC_DOMAIN_HESTON*/, (uint32_t)j, carry, z0, z1);
+        step(z0, z1);
+    }
+    gen.pairs_done((uint32_t)n);
+    double val = heston_value(p, o);
+    if (ANTI)
+        val = 0.5 * (val + heston_value(q, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths
+template <class Real, bool ANTI, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void heston_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const HestonArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = heston_path<ANTI>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // CVA, parallel in the DATE axis.  Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
 // its path.  With the reformulation above the lane's only state is W_j = z_1 + ... + z_j and everything else is a table
 // row of the date, so the walk is a prefix sum followed by independent work: here a path's dates are shared by

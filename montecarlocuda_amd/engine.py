@@ -121,6 +121,15 @@ def _as_barrier(X, o, barrier=None, n_dates=None, kind=None, monitoring=None) ->
     return _lib.BARRIER[X](_as_option(X, o), float(barrier), int(n_dates), kind, monitoring)
 
 
+def _as_heston(X, o, model=None, n_steps=None) -> C.Structure:
+    """mc_heston_*: an option (OptionData or dict; its v is ignored) with the model {v0, kappa, theta, xi, rho} and n_steps, or a
+    dict that carries the model's five fields and "n_steps" itself."""
+    if model is None:
+        model, n_steps = o, o["n_steps"]
+    opt = _as_option(X, o if not isinstance(o, dict) else dict(o, v=o.get("v", 0.0)))
+    return _lib.HESTON[X](opt, *(float(model[f]) for f in ("v0", "kappa", "theta", "xi", "rho")), int(n_steps))
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -373,6 +382,12 @@ class Engine:
         the dates: unbiased for the continuously monitored price, barrier_closed_form).  Honours set_antithetic."""
         return self._run("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
 
+    def heston(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """European call under the Heston model, full-truncation Euler on n_steps equal steps (mc_heston_run_*).  model: a dict
+        with v0, kappa, theta, xi, rho; opt's v is ignored.  Honours set_antithetic; biased by the scheme against
+        heston_closed_form, the price of the continuous model."""
+        return self._run("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
@@ -390,6 +405,8 @@ class Engine:
             return h.struct, h
         if prod == "asian":   # inputs: the option's fields plus "n_dates"
             return _as_asian(precision, inputs), None
+        if prod == "heston":   # inputs: the option's fields plus "v0", "kappa", "theta", "xi", "rho" and "n_steps"
+            return _as_heston(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
             return _as_barrier(precision, inputs), None
         return _as_cva(precision, inputs), None
@@ -417,6 +434,9 @@ class Engine:
     def barrier_paths(self, opt, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out",
                       monitoring="discrete"):
         return self._paths("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
+
+    def heston_paths(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
 
     def normals(self, seed, domain, first_unit, n_units, block=0, precision="f64"):
         npb = 4 if (precision == "f32" or self._normals_f32) else 8
@@ -525,6 +545,13 @@ def barrier_closed_form(opt, barrier, kind="up-and-out", precision="f64"):
     """Discounted Reiner-Rubinstein price of the continuously monitored single-barrier call (no dividend, no rebate; fp64)."""
     p = C.c_double()
     check(getattr(lib(), f"mc_barrier_closed_form_{precision}")(C.byref(_as_barrier(precision, opt, barrier, 1, kind, "continuous")), C.byref(p)))
+    return p.value
+
+
+def heston_closed_form(opt, model, precision="f64"):
+    """Discounted exact price of the European call under the continuous Heston model (no dividend; fp64 quadrature)."""
+    p = C.c_double()
+    check(getattr(lib(), f"mc_heston_closed_form_{precision}")(C.byref(_as_heston(precision, opt, model, 1)), C.byref(p)))
     return p.value
 
 
