@@ -270,7 +270,11 @@ static int context_allocate(mc_context *c)
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipMalloc(&c->partials, sizeof(double2) * ((size_t)MAX_SEGMENTS * c->blocks * MAX_GRID_SCALE + 2)));
     HIPCHK(hipMalloc(&c->tickets, sizeof(uint32_t) * TICKET_WORDS));
-    HIPCHK(hipMemset(c->tickets, 0, sizeof(uint32_t) * TICKET_WORDS));
+    // on the context's own stream, and waited for (as book_buffers does): a fill of device memory on the default stream may still be
+    // pending when hipMemset returns, and a non-blocking stream is not ordered behind it -- landing among the first call's arrivals
+    // it would leave that call short of its `total`, never closed
+    HIPCHK(hipMemsetAsync(c->tickets, 0, sizeof(uint32_t) * TICKET_WORDS, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMalloc(&c->d_triple, 3 * sizeof(double)));
     HIPCHK(hipHostMalloc(&c->h_triple, 3 * sizeof(double), hipHostMallocDefault));
     HIPCHK(hipHostMalloc(&c->h_direct, 12 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));

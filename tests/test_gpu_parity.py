@@ -56,7 +56,10 @@ SEED = 0x4D435F4D49333535
 
 
 def basket_inputs(mc, n, X, rho=0.5):
-    """S=100, w=1/n, vols alternating 0.3/0.2, K=100, r=0.048790164, T=1, equicorrelation."""
+    """S=100, w=1/n, vols alternating 0.3/0.2, K=100, r=0.048790164, T=1, equicorrelation.
+    This market cannot see an index error: a folded matrix entry depends only on its column and its row's parity, base / coef / wg
+    take two values each, so exchanged tiles or assets leave every path bit-identical (test_basket_ref.py writes that down).  The
+    asymmetric markets, per path for every size, estimator and kernel family, are in test_gpu_basket_ref.py."""
     v = [0.3 if i % 2 == 0 else 0.2 for i in range(n)]
     corr = np.full((n, n), rho) + (1 - rho) * np.eye(n)
     L, bad = mc.chol(corr, X)
