@@ -70,6 +70,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_ASIAN 4u
 #define MC_DOMAIN_BARRIER 5u
 #define MC_DOMAIN_HESTON 6u
+#define MC_DOMAIN_HESTON_PATH 7u
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -121,6 +122,15 @@ typedef struct { mc_option_f64 option; double barrier; int n_dates, type, monito
 #define MC_MAX_HESTON_STEPS 4096
 typedef struct { mc_option_f32 option; float v0, kappa, theta, xi, rho; int n_steps; } mc_heston_f32;
 typedef struct { mc_option_f64 option; double v0, kappa, theta, xi, rho; int n_steps; } mc_heston_f64;
+
+/* Path-dependent calls on the Heston walk (see mc_heston_path_run_*): the arithmetic-average call and the single-barrier call
+ * monitored on the dates.  Not in the reference.  heston.n_steps is the TOTAL number of Euler steps; the contract has
+ * n_dates = heston.n_steps / steps_per_date equally spaced dates, so the scheme's step can be finer than the monitoring grid.
+ * barrier_type is one of MC_BARRIER_*; barrier and barrier_type are ignored by MC_HESTON_PATH_ASIAN.  One table value per
+ * date (the Asian call's table). */
+enum { MC_HESTON_PATH_ASIAN = 0, MC_HESTON_PATH_BARRIER = 1 };
+typedef struct { mc_heston_f32 heston; int steps_per_date, payoff, barrier_type; float barrier; } mc_heston_path_f32;
+typedef struct { mc_heston_f64 heston; int steps_per_date, payoff, barrier_type; double barrier; } mc_heston_path_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -399,8 +409,8 @@ int mc_barrier_closed_form_f64(const mc_barrier_f64 *opt, double *price);
  * argument range of the device's exponential (a heuristic guard against absurd inputs, not a bound on the variance); the range
  * errors of the other products.  MC_ERR_UNSUPPORTED: the control
  * variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a context set up for external
- * normals or the launch geometry.  The context stays usable.  No puts, Greeks, book, other discretisation schemes or
- * path-dependent payoffs.  mc_heston_paths_* returns the per-path values (undiscounted; n_paths <= 2^26).
+ * normals or the launch geometry.  The context stays usable.  No puts, Greeks, book or other discretisation schemes;
+ * path-dependent payoffs: mc_heston_path_* below.  mc_heston_paths_* returns the per-path values (undiscounted; n_paths <= 2^26).
  * mc_heston_closed_form_*: the exact price of the call in the CONTINUOUS model (discounted, no dividend) -- not of the Euler
  * scheme, whose bias shrinks with dt.  Heston's P1 / P2 decomposition with the branch-cut-safe ("little Heston trap")
  * characteristic function, integrated in fp64 by 16-point Gauss-Legendre on panels of the fixed width 1 / (4 sd), sd^2 = t times
@@ -420,6 +430,39 @@ int mc_heston_paths_f32(mc_context *ctx, const mc_heston_f32 *opt, uint64_t seed
 int mc_heston_paths_f64(mc_context *ctx, const mc_heston_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 int mc_heston_closed_form_f32(const mc_heston_f32 *opt, double *price);
 int mc_heston_closed_form_f64(const mc_heston_f64 *opt, double *price);
+
+/* ---- Asian and discretely monitored barrier calls under the Heston model ----------------------------------
+ * The walk of mc_heston_run_* on m = heston.n_steps = n_dates * steps_per_date steps: the same step formulas, two normals per
+ * step.  The monitoring dates are t_d = d t / n_dates, d = 1 ... n_dates (t_0 is not monitored); date d falls after step
+ * d * steps_per_date, where the log price is
+ *     x_d = ln s + r t_d - (dt/2) sum_{j <= d spd} V+_{j-1} + sdt sum_{j <= d spd} s_{j-1} z1_j        (spd = steps_per_date)
+ * -- the same real number as the step-by-step x_j of mc_heston_run_*, read from its two running sums.
+ *   MC_HESTON_PATH_ASIAN:    per path, undiscounted, ((1/n_dates) sum_d exp(x_d) - k)^+
+ *   MC_HESTON_PATH_BARRIER:  h = ln barrier, sgn = +1 (up) or -1 (down), d_d = sgn (h - x_d), P = [min_d d_d > 0];
+ *                            knock-out P (exp(x_m) - k)^+, knock-in (1 - P)(exp(x_m) - k)^+.  On a path that crossed at a date the
+ *                            knock-out value is exactly 0 and the knock-in value exactly the payoff.
+ * The barrier is monitored ON THE DATES ONLY.  Continuous monitoring is not offered: the Brownian-bridge survival probability
+ * of mc_barrier_run_* assumes a constant variance between two dates, which under this model is an approximation.
+ * mc_context_set_antithetic: the mean of the value at (z1, z2) and at (-z1, -z2), each direction with its own V, its own sums
+ * and its own running average or minimum; n counts pairs.
+ * Stream: path p is unit p of MC_DOMAIN_HESTON_PATH; step j (1-based) draws entries 2(j-1) % npb and 2(j-1) % npb + 1 of block
+ * 2(j-1) / npb as z1 and z2: the Heston layout under its own domain word.
+ * Path ranges, the finish, call statistics, timing, arming and ordering as for mc_heston_*; several GPUs:
+ * mc_heston_path_launch_* on the ranges of mc_shard_range, the triples added, mc_closing.
+ * MC_ERR_INVALID before anything is enqueued: everything mc_heston_run_* refuses (its exponent-range guard included);
+ * steps_per_date < 1 or not a divisor of heston.n_steps; payoff out of range; for the barrier payoff barrier_type out of
+ * range, barrier <= 0 or non-finite, the spot on or beyond the barrier (up with s >= barrier, down with s <= barrier).
+ * MC_ERR_UNSUPPORTED: the control variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a
+ * context set up for external normals or the launch geometry.  The context stays usable.  No puts, rebates, double barriers,
+ * unequal dates, Greeks or book.  mc_heston_path_paths_* returns the per-path values (undiscounted; n_paths <= 2^26). */
+int mc_heston_path_run_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_path_run_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_path_launch_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                              double *d_triple, void *stream);
+int mc_heston_path_launch_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                              double *d_triple, void *stream);
+int mc_heston_path_paths_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_heston_path_paths_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

@@ -87,6 +87,14 @@ class HestonF64(C.Structure):   # mc_heston_f64
                 ("n_steps", C.c_int)]
 
 
+class HestonPathF32(C.Structure):   # mc_heston_path_f32
+    _fields_ = [("heston", HestonF32), ("steps_per_date", C.c_int), ("payoff", C.c_int), ("barrier_type", C.c_int), ("barrier", C.c_float)]
+
+
+class HestonPathF64(C.Structure):   # mc_heston_path_f64
+    _fields_ = [("heston", HestonF64), ("steps_per_date", C.c_int), ("payoff", C.c_int), ("barrier_type", C.c_int), ("barrier", C.c_double)]
+
+
 class Result(C.Structure):
     _fields_ = [("expected", C.c_double), ("confidence", C.c_double), ("sum", C.c_double), ("sum2", C.c_double),
                 ("n", C.c_uint64), ("kernel_ms", C.c_float), ("wall_ms", C.c_float)]
@@ -125,6 +133,8 @@ CVA = {"f32": CvaF32, "f64": CvaF64}
 ASIAN = {"f32": AsianF32, "f64": AsianF64}
 BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
 HESTON = {"f32": HestonF32, "f64": HestonF64}
+HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
+HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -146,6 +156,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
+    EXPORTS += [f"mc_heston_path_run_{_x}", f"mc_heston_path_launch_{_x}", f"mc_heston_path_paths_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -230,6 +241,9 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]
         getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_heston_path_launch_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_heston_path_run_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_heston_path_paths_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, RP]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

@@ -2377,6 +2377,105 @@ static int heston_enqueue(mc_context *c, const typename HestonIn<Real>::type *v,
 }
 
 // ---------------------------------------------------------------------------------------
+// Asian and discretely monitored barrier calls on the Heston walk: heston_path_kernel, one lane per path, one table value per date
+// ---------------------------------------------------------------------------------------
+template <class Real> struct HestonPathIn;
+template <> struct HestonPathIn<float> { using type = mc_heston_path_f32; };
+template <> struct HestonPathIn<double> { using type = mc_heston_path_f64; };
+
+// what mc_heston_check_* does not know of: the dates, the payoff and the barrier (the rule of mc_barrier_check_*)
+template <class In>
+static int heston_path_check(const In &v)
+{
+    if (int rc = heston_check(v.heston)) return rc;
+    if (v.steps_per_date < 1 || v.heston.n_steps % v.steps_per_date != 0)
+        return fail(MC_ERR_INVALID, "heston path: steps_per_date=%d is below 1 or does not divide n_steps=%d", v.steps_per_date, v.heston.n_steps);
+    if (v.payoff != MC_HESTON_PATH_ASIAN && v.payoff != MC_HESTON_PATH_BARRIER)
+        return fail(MC_ERR_INVALID, "heston path: payoff=%d is neither MC_HESTON_PATH_ASIAN nor MC_HESTON_PATH_BARRIER", v.payoff);
+    if (v.payoff == MC_HESTON_PATH_BARRIER) {
+        const double s = (double)v.heston.option.s, b = (double)v.barrier;
+        if (v.barrier_type < MC_BARRIER_UP_OUT || v.barrier_type > MC_BARRIER_DOWN_IN)
+            return fail(MC_ERR_INVALID, "heston path: barrier_type=%d is none of MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN", v.barrier_type);
+        if (!(b > 0) || !std::isfinite(b))
+            return fail(MC_ERR_INVALID, "heston path: need a finite barrier > 0");
+        if (v.barrier_type <= MC_BARRIER_UP_IN ? s >= b : s <= b)
+            return fail(MC_ERR_INVALID, "heston path: the spot %g is on or beyond the %s barrier %g: the product is then the European call or nothing",
+                        s, v.barrier_type <= MC_BARRIER_UP_IN ? "up" : "down", b);
+    }
+    return MC_OK;
+}
+
+// heston_args' constants and the per-date table in the context's table buffer (cached by content, uploaded only when the inputs
+// change), date d = 1 ... n_dates, t_d = d T / n_dates, folded in fp64 and rounded once:
+//   Asian:    xk_d = ln S0 + r t_d in exponent units, the date's coefficients (av, aw) the maturity's
+//   barrier:  dk_d = sgn (ln B - ln S0 - r t_d) in natural-log units, (av, aw) = sgn (dt/2, -sdt)
+template <class Real>
+static int heston_path_table_ready(mc_context *c, const typename HestonPathIn<Real>::type *v, hipStream_t st, HestonPathArgs<Real> &args)
+{
+    const auto &o = v->heston.option;
+    const double sc = exp_scale<Real>();
+    const int n_dates = v->heston.n_steps / v->steps_per_date;
+    const double m = (double)v->heston.n_steps, dt = (double)o.t / m, sdt = std::sqrt(dt), ln_s0 = std::log((double)o.s);
+    const bool barrier = v->payoff == MC_HESTON_PATH_BARRIER;
+    const double sgn = barrier && v->barrier_type > MC_BARRIER_UP_IN ? -1.0 : 1.0;
+    const double gap = barrier ? std::log((double)v->barrier) - ln_s0 : 0.0;
+    static thread_local std::vector<Real> tab;
+    tab.resize((size_t)n_dates);
+    for (int d = 1; d <= n_dates; ++d) {
+        const double drift = (double)o.r * ((double)o.t * (double)d / (double)n_dates);
+        tab[(size_t)d - 1] = barrier ? (Real)(sgn * (gap - drift)) : (Real)((ln_s0 + drift) * sc);
+    }
+    if (int rc = c->table.upload(c, st, table_key(tab, barrier ? 'Q' : 'H'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    const bool in = barrier && (v->barrier_type == MC_BARRIER_UP_IN || v->barrier_type == MC_BARRIER_DOWN_IN);
+    args.tab = (const Real *)c->table.d;
+    args.steps_per_date = v->steps_per_date;
+    args.av = barrier ? (Real)(sgn * 0.5 * dt) : args.h.av;
+    args.aw = barrier ? (Real)(-sgn * sdt) : args.h.aw;
+    args.inv_m = (Real)(1.0 / (double)n_dates);
+    args.c0 = in ? (Real)1 : (Real)0;
+    args.c1 = in ? (Real)-1 : (Real)1;
+    return MC_OK;
+}
+
+template <class Real>
+static int heston_path_enqueue(mc_context *c, const typename HestonPathIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                               double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "heston path: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "heston path: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "heston path: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_UNSUPPORTED, "heston path: no control variate");
+    if (int rc = heston_path_check(*v)) return rc;
+    HestonPathArgs<Real> args;
+    if (int rc = heston_args<Real>(&v->heston, args.h)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    if (int rc = heston_path_table_ready<Real>(c, v, st, args)) return rc;
+    const bool barrier = v->payoff == MC_HESTON_PATH_BARRIER;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) {
+                if (barrier) launch_sim(prof, heston_path_kernel<Real, true, 1>, g, st, t, args, w, dst);
+                else         launch_sim(prof, heston_path_kernel<Real, true, 0>, g, st, t, args, w, dst);
+            } else {
+                if (barrier) launch_sim(prof, heston_path_kernel<Real, false, 1>, g, st, t, args, w, dst);
+                else         launch_sim(prof, heston_path_kernel<Real, false, 0>, g, st, t, args, w, dst);
+            }
+            return MC_OK;
+        });
+}
+
+// ---------------------------------------------------------------------------------------
 // Greeks of the basket call and of the CVA: secondary kernels, plain estimator, synchronous
 // ---------------------------------------------------------------------------------------
 // the inputs' checks and the constant table of basket_greeks_kernel (and, LR = true, of basket_gamma_kernel), uploaded
@@ -3233,6 +3332,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return heston_enqueue<Real>(c, o, seed, first, n, t, st, d);                                     \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_heston_path_launch_##X(mc_context *c, const mc_heston_path_##X *o, uint64_t seed,      \
+                                             uint64_t first, uint64_t n, double *d_triple, void *stream)     \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return heston_path_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);   \
+    }                                                                                                        \
+    extern "C" int mc_heston_path_run_##X(mc_context *c, const mc_heston_path_##X *o, uint64_t seed,         \
+                                          uint64_t first, uint64_t n, mc_result *out)                        \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->heston.option.r * (double)o->heston.option.t);              \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return heston_path_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                          \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_heston_path_paths_##X(mc_context *c, const mc_heston_path_##X *o, uint64_t seed,       \
+                                            uint64_t first, uint64_t n, Real *h_out)                         \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return heston_path_enqueue<Real>(c, o, seed, first, n, t, st, d);                                \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_normals_##X(mc_context *c, uint64_t seed, uint32_t domain, uint64_t first_unit,        \

@@ -2356,7 +2356,189 @@ __global__ __launch_bounds__(GROUP) void heston_kernel(const Tail /* first argum
 }
 
 // =========================================================================================
-// CVA, parallel in the DATE axis.  Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
+// Path-dependent calls on the Heston walk above: the arithmetic-average call (PAYOFF = 0) and the single-barrier call
+// monitored on the dates (PAYOFF = 1).  Not in the reference.  The walk takes n_steps = n_dates * steps_per_date steps of
+// heston_step; date d (1-based) falls after step d * steps_per_date and reads the log price from the two running sums:
+//   Asian:    x_d = fma(aw, sw, fma(av, sv, xk_d)),   xk_d = ln S0 + r t_d in exponent units;  sum S += E(x_d)
+//   barrier:  d_d = fma(aw, sw, fma(av, sv, dk_d)),   dk_d = sgn (ln B - ln S0 - r t_d), (av, aw) = sgn (dt/2, -sdt), natural-log
+//             units; mn = min(mn, d_d);  P = [mn > 0] by a select;  value = (c0 + c1 P) heston_value (the one exponential)
+// The date's addend comes from the context's constant table (one value per date, folded in fp64 and rounded once) through
+// scalar loads: the date index is wave-uniform, and so is the countdown to the next date -- both live in SGPRs, the date's
+// code sits behind a scalar branch, and the steps between two dates are heston_path's.
+//   ANTI: a second walk on (-z1, -z2) with its own sums and its own running average / minimum; value = mean of the two
+// Stream: domain 7, the Heston layout.  Continuous monitoring is not offered: the Brownian-bridge factor of barrier_kernel
+// assumes a constant variance between two dates.
+// =========================================================================================
+template <class Real>
+struct HestonPathArgs {
+    HestonArgs<Real> h;   // the walk; (x0, av, aw, strike) give the value at maturity
+    const Real *tab;      // n_dates values: xk_d (Asian) or dk_d (barrier)
+    int steps_per_date;
+    Real av, aw;          // the date's coefficients of sum V+ and sum s z1
+    Real inv_m;           // Asian: 1 / n_dates
+    Real c0, c1;          // barrier: value = (c0 + c1 P) payoff
+};
+
+// what a path direction carries besides its HestonSide: sum S over the dates (Asian) or the running minimum distance (barrier)
+template <int PAYOFF, class Real>
+__device__ __forceinline__ Real heston_date_start()
+{
+    return PAYOFF == 0 ? (Real)0 : (Real)__builtin_inf();
+}
+
+__device__ __forceinline__ float min_r(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double min_r(double a, double b) { return min_f64(a, b); }
+
+template <int PAYOFF, class Real>
+__device__ __forceinline__ void heston_date(const HestonSide<Real> &p, Real &acc, Real addend, const HestonPathArgs<Real> &o)
+{
+    const Real x = fma_r(o.aw, p.sw, fma_r(o.av, p.sv, addend));
+    if (PAYOFF == 0)
+        acc += exp_model(x);
+    else
+        acc = min_r(acc, x);
+}
+
+template <int PAYOFF, class Real>
+__device__ __forceinline__ Real heston_path_value(const HestonSide<Real> &p, Real acc, const HestonPathArgs<Real> &o)
+{
+    if (PAYOFF == 0) {
+        const Real a = fma_r(acc, o.inv_m, -o.h.strike);
+        return a > 0 ? a : 0;
+    }
+    const Real P = acc > 0 ? (Real)1 : (Real)0;   // the select, as barrier_value
+    return fma_r(o.c1, P, o.c0) * heston_value(p, o.h);
+}
+
+// fp32: heston_path<float>'s trips, one Philox block = two steps.  After each step the scalar countdown `left` decides whether a
+// date falls there: an odd steps_per_date puts one between the two steps of a block, which is the first of the two branches
+// below and needs no second generator call.  n_steps is a multiple of steps_per_date, so the odd last step ends on a date.
+template <bool ANTI, int PAYOFF, class Gen>
+__device__ __forceinline__ float heston_path_walk(Gen &gen, const HestonPathArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two steps per block");
+    const int n = o.h.n_steps;
+    HestonSide<float> p = {o.h.v0, 0.0f, 0.0f}, q = p;
+    float acc = heston_date_start<PAYOFF, float>(), acc_m = acc;
+    float z[NPB];
+    auto step = [&](float z1, float z2) {
+        const float t = __builtin_fmaf(z2, o.h.c2, o.h.c1 * z1);
+        heston_step(p, z1, t, o.h, 0.0f);
+        if (ANTI)
+            heston_step(q, -z1, -t, o.h, 0.0f);
+    };
+    int d = 0, left = o.steps_per_date;
+    auto date = [&]() {
+        const float addend = o.tab[d];
+        heston_date<PAYOFF>(p, acc, addend, o);
+        if (ANTI)
+            heston_date<PAYOFF>(q, acc_m, addend, o);
+        ++d;
+        left = o.steps_per_date;
+    };
+    int j = 0;
+    for (; j + 2 <= n; j += 2) {
+        gen.normals(w, c0, (uint32_t)(j >> 1), 7u /*MC_DOMAIN_HESTON_PATH*/, z);
+        step(z[0], z[1]);
+        if (--left == 0)   // wave-uniform
+            date();
+        step(z[2], z[3]);
+        if (--left == 0)
+            date();
+    }
+    if (j < n) {   // wave-uniform: the odd last step, which is the last date
+        gen.normals(w, c0, (uint32_t)(j >> 1), 7u /*MC_DOMAIN_HESTON_PATH*/, z);
+        step(z[0], z[1]);
+        date();
+    }
+    float val = heston_path_value<PAYOFF>(p, acc, o);
+    if (ANTI)
+        val = 0.5f * (val + heston_path_value<PAYOFF>(q, acc_m, o));
+    return val;
+}
+
+// fp64: heston_path<double>'s trips (four pairs per trip, then one), the same countdown after every step.
+template <bool ANTI, int PAYOFF, class Gen>
+__device__ __forceinline__ double heston_path_walk(Gen &gen, const HestonPathArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.h.n_steps;
+    HestonSide<double> p = {o.h.v0, 0.0, 0.0}, q = p;
+    double acc = heston_date_start<PAYOFF, double>(), acc_m = acc;
+    const double floor = 0x1p-1000;
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto step = [&](double z1, double z2) {
+        const double t = __builtin_fma(z2, o.h.c2, o.h.c1 * z1);
+        heston_step(p, z1, t, o.h, floor);
+        if (ANTI)
+            heston_step(q, -z1, -t, o.h, floor);
+    };
+    int d = 0, left = o.steps_per_date;
+    auto date = [&]() {
+        const double addend = o.tab[d];
+        heston_date<PAYOFF>(p, acc, addend, o);
+        if (ANTI)
+            heston_date<PAYOFF>(q, acc_m, addend, o);
+        ++d;
+        left = o.steps_per_date;
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 4 <= n; j += 4) {
+            uint32_t g4 = (uint32_t)(j >> 2) << 2;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // heston_path<double>'s tie: a step's generator call starts after the variance of the step before it
+                if (ANTI && k)
+                    asm("" : "+v"(p.V), "+s"(g4));
+                double z0, z1;
+                gen.pair(w, c0, 7u /*MC_DOMAIN_HESTON_PATH*/, g4 | k, carry, z0, z1);
+                step(z0, z1);
+                if (--left == 0)   // wave-uniform
+                    date();
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; ++j) {
+        double z0, z1;
+        gen.pair(w, c0, 7u /*MC_DOMAIN_HESTON_PATH*/, (uint32_t)j, carry, z0, z1);
+        step(z0, z1);
+        if (--left == 0)
+            date();
+    }
+    gen.pairs_done((uint32_t)n);
+    double val = heston_path_value<PAYOFF>(p, acc, o);
+    if (ANTI)
+        val = 0.5 * (val + heston_path_value<PAYOFF>(q, acc_m, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths
+template <class Real, bool ANTI, int PAYOFF, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void heston_path_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const HestonPathArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = heston_path_walk<ANTI, PAYOFF>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
+// CVA, parallel in the DATE axis. Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
 // its path.  With the reformulation above the lane's only state is W_j = z_1 + ... + z_j and everything else is a table
 // row of the date, so the walk is a prefix sum followed by independent work: here a path's dates are shared by
 // L = 2^log2_lanes ADJACENT lanes (L = 2 ... 64).  Per round of CH * L dates, lane `sub` of the path owns the CH dates

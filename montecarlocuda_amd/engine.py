@@ -130,6 +130,19 @@ def _as_heston(X, o, model=None, n_steps=None) -> C.Structure:
     return _lib.HESTON[X](opt, *(float(model[f]) for f in ("v0", "kappa", "theta", "xi", "rho")), int(n_steps))
 
 
+def _as_heston_path(X, o, model=None, n_dates=None, steps_per_date=None, payoff=None, barrier=None, kind=None) -> C.Structure:
+    """mc_heston_path_*: an option and a model as for _as_heston with the contract's n_dates, the Euler steps per date and the payoff
+    ("asian" or "barrier", then with the barrier and its kind), or a dict that carries "n_dates", "steps_per_date", "payoff" and
+    for the barrier "barrier" and optionally "kind" itself."""
+    if model is None:
+        model, n_dates, steps_per_date, payoff = o, o["n_dates"], o["steps_per_date"], o["payoff"]
+        barrier, kind = o.get("barrier"), o.get("kind", "up-and-out")
+    payoff = _lib.HESTON_PATH_PAYOFFS[payoff] if isinstance(payoff, str) else int(payoff)
+    kind = 0 if kind is None else _lib.BARRIER_TYPES[kind] if isinstance(kind, str) else int(kind)
+    h = _as_heston(X, o, model, int(n_dates) * int(steps_per_date))
+    return _lib.HESTON_PATH[X](h, int(steps_per_date), payoff, kind, 0.0 if barrier is None else float(barrier))
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -388,6 +401,18 @@ class Engine:
         heston_closed_form, the price of the continuous model."""
         return self._run("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
 
+    def heston_asian(self, opt, model, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """Arithmetic-average call over n_dates equally spaced dates under the Heston model, full-truncation Euler with
+        steps_per_date steps between two dates (mc_heston_path_run_*).  Honours set_antithetic."""
+        return self._run("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "asian"), seed, first_path, n_paths)
+
+    def heston_barrier(self, opt, model, barrier, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64",
+                       kind="up-and-out") -> Estimate:
+        """Single-barrier call monitored on n_dates equally spaced dates under the Heston model, steps_per_date Euler steps between
+        two dates (mc_heston_path_run_*).  kind as for barrier(); there is no continuous monitoring.  Honours set_antithetic."""
+        return self._run("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
+                         first_path, n_paths)
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
@@ -407,6 +432,8 @@ class Engine:
             return _as_asian(precision, inputs), None
         if prod == "heston":   # inputs: the option's fields plus "v0", "kappa", "theta", "xi", "rho" and "n_steps"
             return _as_heston(precision, inputs), None
+        if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
+            return _as_heston_path(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
             return _as_barrier(precision, inputs), None
         return _as_cva(precision, inputs), None
@@ -437,6 +464,14 @@ class Engine:
 
     def heston_paths(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
+
+    def heston_asian_paths(self, opt, model, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "asian"), seed, first_path, n_paths)
+
+    def heston_barrier_paths(self, opt, model, barrier, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64",
+                             kind="up-and-out"):
+        return self._paths("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
+                           first_path, n_paths)
 
     def normals(self, seed, domain, first_unit, n_units, block=0, precision="f64"):
         npb = 4 if (precision == "f32" or self._normals_f32) else 8
