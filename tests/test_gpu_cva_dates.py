@@ -6,7 +6,8 @@ MonteCarloHost.c printed (tests/golden/ref_mc.json).
 Tolerances are the CVA bounds of tests/test_gpu_parity.py (f64: 1e-13 per path, 1e-12 relative on sums; f32: 2e-5, 3e-6):
 the date-parallel form evaluates the same per-date operations on the same normals and differs only in the association of two
 sums per path -- W_j = z_1 + ... + z_j is formed as (previous rounds + lanes below + own dates) and sum_j dp_j ee_j per lane
-first, then over the lanes."""
+first, then over the lanes.
+Asymmetric markets, the intrinsic date on an even index, the host thresholds of cva_enqueue and the table's reuse: test_gpu_cva_ref.py."""
 import numpy as np
 import pytest
 

@@ -242,7 +242,8 @@ def test_cva_last_date_a_hair_before_maturity_stays_finite(eng, po):
 def test_cva_per_path_and_sums(eng, po, X, n_grid):
     """Grid sizes of the reference driver (cvaOpt.cu:70-75) plus 256 (BASELINE C5) and tiny grids.
     250 in f64 ends with a NEGATIVE residual maturity (last date contributes 0), 256 with exactly 0
-    (intrinsic value), 500 in f32 with a small positive one (SURVEY 2.3 #8)."""
+    (intrinsic value), 500 in f32 with a small positive one.
+    Asymmetric markets, every schedule ending and every lane count per path against the float64 model: test_gpu_cva_ref.py."""
     c = dict(CVA0, n_grid=n_grid)
     n = 3000
     got = f64(eng.cva_paths(c, n, SEED, 11, X))
