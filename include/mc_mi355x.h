@@ -71,6 +71,8 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_BARRIER 5u
 #define MC_DOMAIN_HESTON 6u
 #define MC_DOMAIN_HESTON_PATH 7u
+#define MC_DOMAIN_LOOKBACK 8u
+#define MC_DOMAIN_LOOKBACK_BRIDGE 9u /* the lookback call's uniforms: raw Philox blocks, see mc_lookback_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -114,6 +116,16 @@ enum { MC_BARRIER_UP_OUT = 0, MC_BARRIER_UP_IN = 1, MC_BARRIER_DOWN_OUT = 2, MC_
 enum { MC_MONITOR_DISCRETE = 0, MC_MONITOR_CONTINUOUS = 1 };
 typedef struct { mc_option_f32 option; float barrier; int n_dates, type, monitoring; } mc_barrier_f32;
 typedef struct { mc_option_f64 option; double barrier; int n_dates, type, monitoring; } mc_barrier_f64;
+
+/* Lookback options on n_dates equally spaced dates (the Asian call's dates): the payoff is written on the running maximum or
+ * minimum of the spot, taken on those dates only (MC_MONITOR_DISCRETE) or continuously, by sampling the maximum of the Brownian
+ * bridge between them (MC_MONITOR_CONTINUOUS); see mc_lookback_run_*.  Not in the reference.  option.k is ignored by the
+ * floating-strike types.  The per-date constants sgn j a travel as the Asian call's table does: same cap, same cache argument;
+ * the running maximum is a selection, not a sum, so the cap's rounding argument holds for W_j alone. */
+#define MC_MAX_LOOKBACK_DATES 4096
+enum { MC_LOOKBACK_FLOAT_CALL = 0, MC_LOOKBACK_FLOAT_PUT = 1, MC_LOOKBACK_FIXED_CALL = 2, MC_LOOKBACK_FIXED_PUT = 3 };
+typedef struct { mc_option_f32 option; int n_dates, type, monitoring; } mc_lookback_f32;
+typedef struct { mc_option_f64 option; int n_dates, type, monitoring; } mc_lookback_f64;
 
 /* European call under the Heston stochastic-volatility model, full-truncation Euler on n_steps equal steps (see
  * mc_heston_run_*).  Not in the reference.  option.v is ignored: the variance starts at v0.  No constant table: every per-step
@@ -388,6 +400,56 @@ int mc_barrier_paths_f32(mc_context *ctx, const mc_barrier_f32 *opt, uint64_t se
 int mc_barrier_paths_f64(mc_context *ctx, const mc_barrier_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 int mc_barrier_closed_form_f32(const mc_barrier_f32 *opt, double *price);
 int mc_barrier_closed_form_f64(const mc_barrier_f64 *opt, double *price);
+
+/* ---- lookback options: discrete and Brownian-bridge continuous extrema -----------------------------------
+ * The Asian call's walk on m = n_dates dates: dt = t/m, a = (r - v^2/2) dt, bx = v sqrt(dt), W_j = z_1 + ... + z_j,
+ * x_j = ln S_j = ln S0 + j a + bx W_j, x_0 = ln S0.  With sgn = +1 when the payoff is on the maximum and -1 when it is on the
+ * minimum, the signed log excursion is y_j = sgn (x_j - x_0) = sgn (j a + bx W_j), y_0 = 0.
+ *   discrete:    Y = max_{1<=j<=m} y_j                                        (t_0 is not monitored)
+ *   continuous:  Y = max_{1<=j<=m} M_j,  M_j = (y_{j-1} + y_j + sqrt((y_j - y_{j-1})^2 + bx^2 E_j)) / 2,  E_j = -2 ln u_j, u_j
+ *                the date's uniform: the inverse of the bridge law P(max <= y | y_{j-1}, y_j) = 1 - exp(-2 (y - y_{j-1})(y - y_j) / bx^2)
+ *                (the law behind the barrier call's survival factor), so the estimator is unbiased for the continuously
+ *                monitored price at ANY n_dates, even 1.  M_j >= max(y_{j-1}, y_j): t_0 is included, and continuous >=
+ *                discrete on every path.  Needs v > 0.
+ *   ext = S0 exp(sgn Y): the running maximum (sgn = +1) or minimum (sgn = -1);  S_T = exp(x_m).
+ *   per-path value, undiscounted:   MC_LOOKBACK_FLOAT_CALL  sgn -1  max(S_T - ext, 0)     MC_LOOKBACK_FLOAT_PUT  sgn +1  max(ext - S_T, 0)
+ *                                   MC_LOOKBACK_FIXED_CALL  sgn +1  max(ext - k, 0)       MC_LOOKBACK_FIXED_PUT  sgn -1  max(k - ext, 0)
+ * mc_context_set_antithetic: the mean of the value at z and at -z, both directions on the SAME E_j (any coupling of the
+ * bridge draws is unbiased; sharing them halves the uniform work); n counts pairs.
+ * Stream: path p is unit p of MC_DOMAIN_LOOKBACK, date j (1-based) draws entry (j - 1) % npb of block (j - 1) / npb: the Asian
+ * layout under its own domain word.  The bridge uniforms, drawn by the continuous form only, are RAW Philox blocks of the same
+ * unit in MC_DOMAIN_LOOKBACK_BRIDGE.  f32: date j takes word (j - 1) % 4 of block (j - 1) / 4, u = fmaf((float) word, 2^-32, 2^-33),
+ * in (0, 1] (u = 1 gives E = 0, which is valid).  f64: date j takes words 2 ((j - 1) % 2) and 2 ((j - 1) % 2) + 1 of
+ * block (j - 1) / 2 as (lo, hi) of u = (((hi:lo) >> 12) + 1/2) 2^-52, strictly inside (0, 1).  A path's value depends on (seed,
+ * global path index, inputs) only.  Path ranges, the finish, timing, arming and ordering as for the other products; several
+ * GPUs as for the Asian call.
+ * mc_lookback_closed_form_*: the discounted price of the CONTINUOUS product at inception (Goldman-Sosin-Gatto for the floating
+ * strikes, Conze-Viswanathan for the fixed ones; no dividend; fp64, Phi by erfc; ignores n_dates and monitoring; usable without
+ * a GPU).  With D = e^{-rt}, c = v^2/(2r), g = 2r sqrt(t)/v, a1 = (r + v^2/2) sqrt(t)/v, a2 = a1 - v sqrt(t),
+ * d1 = (ln(s/k) + (r + v^2/2) t)/(v sqrt(t)), p = (s/k)^(-2r/v^2):
+ *   floating call  s Phi(a1) - s D Phi(a2) + s D c [Phi(g - a1) - e^{rt} Phi(-a1)]
+ *   floating put   s D Phi(-a2) - s Phi(-a1) + s D c [e^{rt} Phi(a1) - Phi(a1 - g)]
+ *   fixed call     k <= s: floating put + s - D k;   k > s: s Phi(d1) - k D Phi(d1 - v sqrt(t)) + s D c [e^{rt} Phi(d1) - p Phi(d1 - g)]
+ *   fixed put      k >= s: floating call - s + D k;  k < s: k D Phi(v sqrt(t) - d1) - s Phi(-d1) + s D c [p Phi(g - d1) - e^{rt} Phi(-d1)]
+ * It needs v > 0 (and k > 0 for the fixed types) and returns MC_ERR_INVALID for r == 0 (the limit exists but is not
+ * implemented); the bracket cancels for small |r|, at about 1e-16 v^2/(2|r|) relative.
+ * MC_ERR_INVALID before anything is enqueued: n_dates outside [1, MC_MAX_LOOKBACK_DATES]; type or monitoring out of range;
+ * s <= 0, t <= 0, v < 0 or a non-finite input; k <= 0 or non-finite for the fixed types; continuous monitoring with v == 0;
+ * drift and volatility that put the simulated spot outside the range of a double; the range errors of the other products.
+ * MC_ERR_UNSUPPORTED: the control variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a
+ * context set up for external normals or the launch geometry.  The context stays usable.  No partial lookback period, no
+ * extremum carried in from before t_0, no unequal dates, no Greeks.
+ * mc_lookback_paths_* returns the per-path values (undiscounted; n_paths <= 2^26). */
+int mc_lookback_run_f32(mc_context *ctx, const mc_lookback_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_lookback_run_f64(mc_context *ctx, const mc_lookback_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_lookback_launch_f32(mc_context *ctx, const mc_lookback_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_lookback_launch_f64(mc_context *ctx, const mc_lookback_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_lookback_paths_f32(mc_context *ctx, const mc_lookback_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_lookback_paths_f64(mc_context *ctx, const mc_lookback_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_lookback_closed_form_f32(const mc_lookback_f32 *opt, double *price);
+int mc_lookback_closed_form_f64(const mc_lookback_f64 *opt, double *price);
 
 /* ---- European call under the Heston model: full-truncation Euler in log space -----------------------------
  * dS = r S dt + sqrt(V) S dW1,  dV = kappa (theta - V) dt + xi sqrt(V) dW2,  corr(dW1, dW2) = rho,  V(0) = v0.

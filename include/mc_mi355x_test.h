@@ -6,7 +6,7 @@
  * deliberately does not have -- which is why they are kept out of the public header.
  *   - the simulation kernels on a caller-supplied normal stream (mc_*_from_normals_*): how the reference's own glibc
  *     normal stream is pushed through the HIP hot kernels and compared with numbers the compiled reference printed;
- *   - generator dumps: Philox/XORWOW normals and words (mc_normals_*, mc_xorwow_words, mc_grid_normals);
+ *   - generator dumps: Philox/XORWOW normals and words (mc_normals_*, mc_words, mc_xorwow_words, mc_grid_normals);
  *   - the launch-geometry mode's two forms side by side: mc_context_set_grid_form, per-path dumps mc_*_paths_grid_*.
  */
 #ifndef MC_MI355X_TEST_H_
@@ -31,6 +31,12 @@ int mc_normals_f32(mc_context *ctx, uint64_t seed, uint32_t domain, uint64_t fir
                    uint64_t n_units, uint32_t block, float *h_out);
 int mc_normals_f64(mc_context *ctx, uint64_t seed, uint32_t domain, uint64_t first_unit,
                    uint64_t n_units, uint32_t block, double *h_out);
+
+/* The raw Philox words of blocks first_block .. first_block + n_blocks - 1 of each unit first_unit .. first_unit + n_units - 1
+ * of `domain`, four per block, unit-major, to the HOST array h_out (n_units * n_blocks * 4 words, at most 2^26): what the tests
+ * rebuild the lookback call's bridge uniforms from. */
+int mc_words(mc_context *ctx, uint64_t seed, uint32_t domain, uint64_t first_unit, uint64_t n_units, uint32_t first_block,
+             uint32_t n_blocks, uint32_t *h_out);
 
 /* The first `count` normals of every thread's stream: h_out[(b * num_threads + t) * count + k] (tests). */
 int mc_grid_normals(mc_context *ctx, int num_blocks, int num_threads, uint32_t count, float *h_out);

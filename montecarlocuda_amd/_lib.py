@@ -16,10 +16,13 @@ LEGACY = {"f64": os.path.join(CSRC, "libmcgpu_f64.so"), "f32": os.path.join(CSRC
 MC_OK = 0
 MC_DEFAULT_SEED = 0x4D435F4D49333535
 DOMAIN_VANILLA, DOMAIN_BASKET, DOMAIN_CVA, DOMAIN_ASIAN, DOMAIN_BARRIER, DOMAIN_HESTON = 1, 2, 3, 4, 5, 6
+DOMAIN_LOOKBACK, DOMAIN_LOOKBACK_BRIDGE = 8, 9   # normals; the continuous form's bridge uniforms (raw Philox blocks)
 MAX_ASIAN_DATES = 4096   # MC_MAX_ASIAN_DATES
 MAX_BARRIER_DATES = 4096   # MC_MAX_BARRIER_DATES
 MAX_HESTON_STEPS = 4096   # MC_MAX_HESTON_STEPS
+MAX_LOOKBACK_DATES = 4096   # MC_MAX_LOOKBACK_DATES
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
+LOOKBACK_TYPES = {"floating-call": 0, "floating-put": 1, "fixed-call": 2, "fixed-put": 3}   # MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
 MAX_ASSETS = 16          # register-resident basket kernels
 MAX_ASSETS_GENERIC = 64  # LDS-staged generic kernel beyond that
@@ -77,6 +80,14 @@ class BarrierF64(C.Structure):   # mc_barrier_f64
     _fields_ = [("option", OptionF64), ("barrier", C.c_double), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
 
 
+class LookbackF32(C.Structure):   # mc_lookback_f32
+    _fields_ = [("option", OptionF32), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
+
+
+class LookbackF64(C.Structure):   # mc_lookback_f64
+    _fields_ = [("option", OptionF64), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
+
+
 class HestonF32(C.Structure):   # mc_heston_f32
     _fields_ = [("option", OptionF32), ("v0", C.c_float), ("kappa", C.c_float), ("theta", C.c_float), ("xi", C.c_float), ("rho", C.c_float),
                 ("n_steps", C.c_int)]
@@ -132,6 +143,7 @@ BASKET = {"f32": BasketF32, "f64": BasketF64}
 CVA = {"f32": CvaF32, "f64": CvaF64}
 ASIAN = {"f32": AsianF32, "f64": AsianF64}
 BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
+LOOKBACK = {"f32": LookbackF32, "f64": LookbackF64}
 HESTON = {"f32": HestonF32, "f64": HestonF64}
 HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
@@ -144,7 +156,7 @@ EXPORTS = ["mc_last_error", "mc_device_count", "mc_device_pci_bus_id", "mc_conte
            "mc_context_order", "mc_context_idle", "mc_context_arm_direct", "mc_context_publish", "mc_context_set_generator",
            "mc_context_set_normals", "mc_context_set_cva_date_lanes", "mc_basket_control_mean_f32", "mc_basket_control_mean_f64", "mc_closing", "mc_shard_range",
            "mc_chol_f32", "mc_chol_f64", "mc_factor_from_cov_f32", "mc_factor_from_cov_f64"]
-TEST_EXPORTS = ["mc_xorwow_words", "mc_grid_normals", "mc_context_set_grid_form"]
+TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_set_grid_form"]
 for _x in ("f32", "f64"):
     for _p in ("vanilla", "basket", "cva"):
         EXPORTS += [f"mc_{_p}_launch_{_x}", f"mc_{_p}_run_{_x}", f"mc_{_p}_paths_{_x}"]
@@ -155,6 +167,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_vanilla_book_run_{_x}", f"mc_vanilla_book_launch_{_x}"]
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
+    EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
     EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
     EXPORTS += [f"mc_heston_path_run_{_x}", f"mc_heston_path_launch_{_x}", f"mc_heston_path_paths_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
@@ -194,6 +207,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.mc_context_set_cva_date_lanes.argtypes = [ctx, C.c_int]
     L.mc_grid_normals.argtypes = [ctx, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
     L.mc_context_set_grid_form.argtypes = [ctx, C.c_int]
+    L.mc_words.argtypes = [ctx, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.mc_xorwow_words.argtypes = [ctx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     for X in ("f32", "f64"):
         getattr(L, f"mc_basket_control_mean_{X}").argtypes = [C.POINTER(BASKET[X]), C.POINTER(C.c_double)]
@@ -237,6 +251,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_barrier_run_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_barrier_paths_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, RP]
         getattr(L, f"mc_barrier_closed_form_{X}").argtypes = [C.POINTER(BARRIER[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_lookback_launch_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_lookback_run_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_lookback_paths_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_lookback_closed_form_{X}").argtypes = [C.POINTER(LOOKBACK[X]), C.POINTER(C.c_double)]
         getattr(L, f"mc_heston_launch_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]

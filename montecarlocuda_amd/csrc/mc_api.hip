@@ -84,7 +84,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a generic basket's folded constants, a basket's Greeks table
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // generator: Philox (counter-based, stateless) or XORWOW (one sequence per lane: mc_rng.hpp GenXorwow)
@@ -367,12 +367,12 @@ extern "C" int mc_context_describe(const mc_context *c, char *buf, int len)
     snprintf(buf, (size_t)len,
              "mc_context config: device=%d \"%s\" CUs=%d clock_mhz=%d blocks=%d finish=%s f64_normals=%s rng=%s antithetic=%d control_variate=%d timing=%d "
              "grid_form=%s basket_static_max=f32:%d,f64:%d basket_tiled_min=%d basket_mfma=%d grid_sub=%d(0=auto) vanilla_units_per_lane=%d cva_date_lanes=%d(0=auto) "
-             "asian_dates_max=%d barrier_dates_max=%d heston_steps_max=%d created_in_ms=%.1f",
+             "asian_dates_max=%d barrier_dates_max=%d heston_steps_max=%d lookback_dates_max=%d created_in_ms=%.1f",
              c->device, c->name, c->compute_units, c->clock_mhz, c->blocks, c->fused ? "fused" : "kernel", c->normals_f32 ? "f32" : "native",
              c->rng == MC_RNG_XORWOW ? "xorwow" : "philox", (int)c->antithetic, (int)c->control, (int)c->timing,
              c->grid_form == MC_GRID_FORM_STAGED ? "staged" : (c->grid_form == MC_GRID_FORM_FUSED ? "fused" : "auto"), basket_static_max<float>(),
              basket_static_max<double>(), basket_tiled_min(), (int)basket_mfma(), env_int("MC_GRID_SUB", 0, 0, 32), vanilla_units_per_lane(), c->cva_date_lanes,
-             MC_MAX_ASIAN_DATES, MC_MAX_BARRIER_DATES, MC_MAX_HESTON_STEPS, c->create_ms);
+             MC_MAX_ASIAN_DATES, MC_MAX_BARRIER_DATES, MC_MAX_HESTON_STEPS, MC_MAX_LOOKBACK_DATES, c->create_ms);
     return MC_OK;
 }
 
@@ -2308,8 +2308,89 @@ static int barrier_enqueue(mc_context *c, const typename BarrierIn<Real>::type *
 }
 
 // ---------------------------------------------------------------------------------------
-// European call under the Heston model (full-truncation Euler): heston_kernel, one lane per path, no table
+// Lookback options, discrete or Brownian-bridge continuous extrema: lookback_kernel, one lane per path
 // ---------------------------------------------------------------------------------------
+template <class Real> struct LookbackIn;
+template <> struct LookbackIn<float> { using type = mc_lookback_f32; };
+template <> struct LookbackIn<double> { using type = mc_lookback_f64; };
+static int lookback_check(const mc_lookback_f32 &o) { return mc_lookback_check_f32(&o); }
+static int lookback_check(const mc_lookback_f64 &o) { return mc_lookback_check_f64(&o); }
+
+// The range check, the constants folded in fp64 and rounded once, and the per-date table yk_j = sgn j a in the walk's units,
+// j = 1 ... n_dates, in the context's table buffer: cached by content, uploaded only when the inputs change.  The walk's unit is
+// the natural log, except in the fp64 continuous form, which walks in units of bx (lookback_kernel).  Maximum or minimum lives
+// in the table and in the sign of sbx; the payoff's sign and its second term in (q, floating).
+template <class Real>
+static int lookback_table_ready(mc_context *c, const typename LookbackIn<Real>::type *v, hipStream_t st, LookbackArgs<Real> &args)
+{
+    const auto &o = v->option;
+    const double sc = exp_scale<Real>();
+    const double m = (double)v->n_dates, dt = (double)o.t / m;
+    const double a = ((double)o.r - 0.5 * (double)o.v * (double)o.v) * dt, bx = (double)o.v * std::sqrt(dt), ln_s0 = std::log((double)o.s);
+    const bool cont = v->monitoring == MC_MONITOR_CONTINUOUS;
+    const bool on_max = v->type == MC_LOOKBACK_FLOAT_PUT || v->type == MC_LOOKBACK_FIXED_CALL;
+    const bool floating = v->type <= MC_LOOKBACK_FLOAT_PUT;
+    const double sgn = on_max ? 1.0 : -1.0;
+    const double unit = cont && sizeof(Real) == 8 ? bx : 1.0;
+    // as for the barrier call: only the hard limit of the device's exp is enforced (a bridge maximum lies within bx sqrt(E_j) / 2 of
+    // its interval's ends); in units of bx the table must stay finite and its squares inside a double
+    if (!(std::fabs(ln_s0) + m * (std::fabs(a) + bx * Z_MAX_F64) + bx * Z_MAX_F64 < EXP_F64_ARG_LIMIT) || !(m * std::fabs(a) / unit < 1e100))
+        return fail(MC_ERR_INVALID, "lookback: drift and volatility put the simulated spot outside the range of a double");
+    static thread_local std::vector<Real> tab;
+    tab.resize((size_t)v->n_dates);
+    for (int j = 1; j <= v->n_dates; ++j)
+        tab[(size_t)j - 1] = (Real)(sgn * (double)j * a / unit);
+    if (int rc = c->table.upload(c, st, table_key(tab, 'L'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    args.yk = (const Real *)c->table.d;
+    args.n_dates = v->n_dates;
+    args.sbx = (Real)(sgn * bx / unit);
+    args.e2 = cont ? (Real)(-2.0 * M_LN2 * bx * bx) : (Real)0;
+    args.x0 = (Real)(ln_s0 * sc);
+    args.es = (Real)(sgn * unit * (cont ? 0.5 : 1.0) * sc);
+    args.eT = (Real)(sgn * unit * sc);
+    args.strike = o.k;
+    args.q = (Real)sgn;   // the two payoffs on the maximum are ext - R, the two on the minimum R - ext
+    args.floating = floating ? 1 : 0;
+    return MC_OK;
+}
+
+template <class Real>
+static int lookback_enqueue(mc_context *c, const typename LookbackIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                            double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "lookback: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "lookback: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "lookback: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_UNSUPPORTED, "lookback: no control variate");
+    if (int rc = lookback_check(*v)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    LookbackArgs<Real> args;
+    if (int rc = lookback_table_ready<Real>(c, v, st, args)) return rc;
+    const bool cont = v->monitoring == MC_MONITOR_CONTINUOUS;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) {
+                if (cont) launch_sim(prof, lookback_kernel<Real, true, true>, g, st, t, args, w, dst);
+                else      launch_sim(prof, lookback_kernel<Real, true, false>, g, st, t, args, w, dst);
+            } else {
+                if (cont) launch_sim(prof, lookback_kernel<Real, false, true>, g, st, t, args, w, dst);
+                else      launch_sim(prof, lookback_kernel<Real, false, false>, g, st, t, args, w, dst);
+            }
+            return MC_OK;
+        });
+}
+
 template <class Real> struct HestonIn;
 template <> struct HestonIn<float> { using type = mc_heston_f32; };
 template <> struct HestonIn<double> { using type = mc_heston_f64; };
@@ -3310,6 +3391,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
             return barrier_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
         });                                                                                                  \
     }                                                                                                        \
+    extern "C" int mc_lookback_launch_##X(mc_context *c, const mc_lookback_##X *o, uint64_t seed, uint64_t first,\
+                                          uint64_t n, double *d_triple, void *stream)                        \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return lookback_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);      \
+    }                                                                                                        \
+    extern "C" int mc_lookback_run_##X(mc_context *c, const mc_lookback_##X *o, uint64_t seed, uint64_t first,\
+                                       uint64_t n, mc_result *out)                                           \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->option.r * (double)o->option.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return lookback_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                             \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_lookback_paths_##X(mc_context *c, const mc_lookback_##X *o, uint64_t seed, uint64_t first,\
+                                         uint64_t n, Real *h_out)                                            \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return lookback_enqueue<Real>(c, o, seed, first, n, t, st, d);                                   \
+        });                                                                                                  \
+    }                                                                                                        \
     extern "C" int mc_heston_launch_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first,\
                                         uint64_t n, double *d_triple, void *stream)                          \
     {                                                                                                        \
@@ -3382,6 +3487,27 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
 
 MC_DEFINE_PRODUCT(f32, float)
 MC_DEFINE_PRODUCT(f64, double)
+
+// The raw Philox words of blocks first_block ... first_block + n_blocks - 1 of each unit (test hook, mc_mi355x_test.h)
+extern "C" int mc_words(mc_context *c, uint64_t seed, uint32_t domain, uint64_t first_unit, uint64_t n_units, uint32_t first_block,
+                        uint32_t n_blocks, uint32_t *h_out)
+{
+    if (int rc = check_common(c, h_out, first_unit, n_units, h_out)) return rc;
+    if (n_blocks == 0 || first_block + n_blocks < first_block || n_units > MAX_DUMP_PATHS || n_units * n_blocks > MAX_DUMP_PATHS / 4)
+        return fail(MC_ERR_INVALID, "mc_words: need n_blocks >= 1, blocks below 2^32 and at most 2^26 words");
+    return dump_sync<uint32_t>(c, n_units * n_blocks * 4u, h_out, [&](hipStream_t st, double *, uint32_t *d) -> int {
+        std::vector<Segment> segs;
+        if (int rc = plan_segments(first_unit, n_units, segs)) return rc;
+        uint64_t done = 0;
+        for (const Segment &s : segs) {
+            const Work w = make_work(seed, s, 0, 0);
+            words_kernel<<<grid_for(c->blocks, s.count), GROUP, 0, st>>>(w, domain, first_block, n_blocks, d + done * n_blocks * 4u);
+            done += s.count;
+        }
+        HIPCHK(hipGetLastError());
+        return MC_OK;
+    });
+}
 MC_DEFINE_FROM_NORMALS(f32, float)
 MC_DEFINE_GRID(f32, float)
 MC_DEFINE_FROM_NORMALS(f64, double)

@@ -11,6 +11,7 @@
  *   mc_basket_control_mean_* closed-form mean of the geometric-basket control variate
  *   mc_asian_control_mean_*  closed-form mean of the geometric-average control variate of the Asian call
  *   mc_barrier_closed_form_* Reiner-Rubinstein price of the continuously monitored single-barrier call
+ *   mc_lookback_closed_form_* Goldman-Sosin-Gatto / Conze-Viswanathan prices of the continuously monitored lookbacks
  *   mc_heston_closed_form_*  exact price of the European call under the Heston model (Gauss-Legendre quadrature)
  *   mc_last_error / mc_internal_fail   the per-thread error text of whichever library this object is linked into
  */
@@ -121,6 +122,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define BASKET mc_basket_f32
 #define ASIAN mc_asian_f32
 #define BARRIER mc_barrier_f32
+#define LOOKBACK mc_lookback_f32
 #define HESTON mc_heston_f32
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -129,6 +131,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef BASKET
 #undef ASIAN
 #undef BARRIER
+#undef LOOKBACK
 #undef HESTON
 
 #define REAL double
@@ -137,6 +140,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define BASKET mc_basket_f64
 #define ASIAN mc_asian_f64
 #define BARRIER mc_barrier_f64
+#define LOOKBACK mc_lookback_f64
 #define HESTON mc_heston_f64
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -145,4 +149,5 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef BASKET
 #undef ASIAN
 #undef BARRIER
+#undef LOOKBACK
 #undef HESTON

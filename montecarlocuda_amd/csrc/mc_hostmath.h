@@ -10,6 +10,9 @@ int mc_internal_fail(int code, const char *fmt, ...) __attribute__((format(print
 /* The input checks of the barrier call, shared by mc_barrier_closed_form_* and the GPU entry points (not exported). */
 int mc_barrier_check_f32(const mc_barrier_f32 *o, int need_vol);
 int mc_barrier_check_f64(const mc_barrier_f64 *o, int need_vol);
+/* The input checks of the lookback options, shared by mc_lookback_closed_form_* and the GPU entry points (not exported). */
+int mc_lookback_check_f32(const mc_lookback_f32 *o);
+int mc_lookback_check_f64(const mc_lookback_f64 *o);
 /* The input checks of the Heston call, shared by mc_heston_closed_form_* and the GPU entry points (not exported). */
 int mc_heston_check_f32(const mc_heston_f32 *o);
 int mc_heston_check_f64(const mc_heston_f64 *o);

@@ -181,6 +181,63 @@ int FN(mc_barrier_closed_form)(const BARRIER *o, double *price)
     return MC_OK;
 }
 
+/* The inputs every lookback entry point refuses (see mc_mi355x.h).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_lookback_check)(const LOOKBACK *o)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    if (o->n_dates < 1 || o->n_dates > MC_MAX_LOOKBACK_DATES)
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: n_dates=%d outside [1, %d]", o->n_dates, MC_MAX_LOOKBACK_DATES);
+    if (o->type < MC_LOOKBACK_FLOAT_CALL || o->type > MC_LOOKBACK_FIXED_PUT)
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: type=%d is none of MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT", o->type);
+    if (o->monitoring != MC_MONITOR_DISCRETE && o->monitoring != MC_MONITOR_CONTINUOUS)
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: monitoring=%d is neither MC_MONITOR_DISCRETE nor MC_MONITOR_CONTINUOUS", o->monitoring);
+    if (!(s > 0) || !(t > 0) || !(v >= 0) || !isfinite(s) || !isfinite(t) || !isfinite(r) || !isfinite(v))
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: need s>0, t>0, v>=0 and finite inputs");
+    if (o->type >= MC_LOOKBACK_FIXED_CALL && (!(k > 0) || !isfinite(k)))
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: the fixed-strike types need a finite k > 0");
+    if (o->monitoring == MC_MONITOR_CONTINUOUS && !(v > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "lookback: continuous monitoring needs v != 0");
+    return MC_OK;
+}
+
+/* Discounted price at inception of the continuously monitored lookback (Goldman-Sosin-Gatto for the floating strikes,
+ * Conze-Viswanathan for the fixed ones; no dividend), fp64, Phi by erfc.  The formulas are stated in mc_mi355x.h. */
+int FN(mc_lookback_closed_form)(const LOOKBACK *o, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "lookback closed form: NULL argument");
+    LOOKBACK one = *o;
+    one.n_dates = 1, one.monitoring = MC_MONITOR_CONTINUOUS;   /* both ignored here; v > 0 is needed */
+    int rc = FN(mc_lookback_check)(&one);
+    if (rc != MC_OK)
+        return rc;
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    if (r == 0)
+        return mc_internal_fail(MC_ERR_INVALID, "lookback closed form: the limit r -> 0 is not implemented");
+#define MC_PHI(x) (0.5 * erfc(-(x) / sqrt(2.0)))
+    const double D = exp(-r * t), G = exp(r * t), sd = v * sqrt(t), c = v * v / (2.0 * r), g = 2.0 * r * sqrt(t) / v;
+    const double a1 = (r + 0.5 * v * v) * sqrt(t) / v, a2 = a1 - sd;
+    const double float_call = s * MC_PHI(a1) - s * D * MC_PHI(a2) + s * D * c * (MC_PHI(g - a1) - G * MC_PHI(-a1));
+    const double float_put = s * D * MC_PHI(-a2) - s * MC_PHI(-a1) + s * D * c * (G * MC_PHI(a1) - MC_PHI(a1 - g));
+    double out;
+    if (o->type == MC_LOOKBACK_FLOAT_CALL) {
+        out = float_call;
+    } else if (o->type == MC_LOOKBACK_FLOAT_PUT) {
+        out = float_put;
+    } else {
+        const double d1 = (log(s / k) + (r + 0.5 * v * v) * t) / sd, p = exp(-2.0 * r / (v * v) * log(s / k));
+        if (o->type == MC_LOOKBACK_FIXED_CALL)
+            out = k <= s ? float_put + s - D * k
+                         : s * MC_PHI(d1) - k * D * MC_PHI(d1 - sd) + s * D * c * (G * MC_PHI(d1) - p * MC_PHI(d1 - g));
+        else
+            out = k >= s ? float_call - s + D * k
+                         : k * D * MC_PHI(sd - d1) - s * MC_PHI(-d1) + s * D * c * (p * MC_PHI(g - d1) - G * MC_PHI(-d1));
+    }
+#undef MC_PHI
+    *price = out;
+    return MC_OK;
+}
+
 /* The inputs every Heston entry point refuses (see mc_mi355x.h).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
 __attribute__((visibility("hidden"))) int FN(mc_heston_check)(const HESTON *o)
 {

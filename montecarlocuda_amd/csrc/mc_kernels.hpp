@@ -2179,6 +2179,244 @@ __global__ __launch_bounds__(GROUP) void barrier_kernel(const Tail /* first argu
 }
 
 // =========================================================================================
+// Lookback options on m equally spaced dates: the payoff is written on the running maximum or minimum of the spot, taken on
+// the dates (CONT = false) or continuously, by sampling the maximum of the Brownian bridge between them (CONT = true).  Not in
+// the reference.  barrier_path's walk in LOG space: the lane's state is W_j and the running maximum of the signed excursion
+//   y_j = sgn (ln S_j - ln S0) = fma(W_j, sbx, yk_j),   sbx = sgn bx,   yk_j = sgn j a      (y_0 = 0)
+// (yk_j from the per-date table, folded in fp64 and rounded once; wave-uniform j: scalar loads, the fma's one scalar operand).
+// sgn = +1 looks at the maximum, -1 at the minimum: the direction lives in the table and in the sign of sbx, both run the same code.
+//   discrete:    Y = max_{j>=1} y_j                                             one fma and one max per date
+//   continuous:  Y = max_j M_j,  2 M_j = y_{j-1} + y_j + sqrt((y_j - y_{j-1})^2 + bx^2 E_j),  E_j = -2 ln u_j: the loop keeps 2 M_j
+//                (M_j >= max(y_{j-1}, y_j): the endpoints need no max of their own) and the half goes into the exponent's factor.
+//                fp32 walks in natural-log units with bx^2 E_j = e2 log2 u_j (e2 = -2 ln2 bx^2 from the host, box_muller_f32's
+//                scale2); fp64 walks in units of bx (sbx = sgn, yk_j = sgn j a / bx), so that sqrt_pos's radicand is
+//                (z_j + a/bx)^2 + E_j >= E_j >= 2^-52 whatever the volatility, and the unit goes into the exponent's factor too.
+//   ext = S0 E(x0 + es Y) the extremum, S_T = E(x0 + eT y_m) from the walk's own last excursion (so S_T <= the maximum and >= the
+//   minimum in floating point as well), value = max(q (ext - R), 0), R = S_T (floating strike) or K (fixed): q and the choice of
+//   R are wave-uniform numbers, the four types run the same kernels.
+//   ANTI: the same at -z (y^-_j = fma(W_j, -sbx, yk_j)) with the SAME E_j, value = mean of the two
+// Stream: normals domain 8, date j (0-based here) = entry j % NPB of block j / NPB: the Asian layout.  Bridge uniforms domain 9,
+// raw Philox blocks of the same unit: fp32 date j = word j % 4 of block j / 4, fp64 date j = words 2 (j % 2), 2 (j % 2) + 1 of block j / 2.
+// =========================================================================================
+template <class Real>
+struct LookbackArgs {
+    const Real *yk;   // n_dates values: sgn (j + 1) a in the walk's units
+    int n_dates;
+    Real sbx;         // sgn v sqrt(dt) in the walk's units (fp64 continuous: sgn alone)
+    Real e2;          // fp32 continuous: -2 ln2 bx^2; otherwise unused
+    Real x0;          // ln S0 in exponent units (natural log in f64, log2 in f32)
+    Real es;          // ln ext = x0 + es Y in exponent units: sgn times the walk's unit, halved under CONT (Y is then max 2 M_j)
+    Real eT;          // ln S_T = x0 + eT y_m in exponent units: sgn times the walk's unit
+    Real strike;
+    Real q;           // +1: max(ext - R, 0), -1: max(R - ext, 0)
+    int floating;     // R = S_T (1) or the strike (0)
+};
+
+template <class Real>
+__device__ __forceinline__ Real lookback_value(Real Y, Real y_last, const LookbackArgs<Real> &o)
+{
+    const Real ext = exp_model(fma_r(Y, o.es, o.x0));
+    const Real R = o.floating ? exp_model(fma_r(y_last, o.eT, o.x0)) : o.strike;   // wave-uniform choice
+    const Real d = o.q * (ext - R);
+    return d > 0 ? d : 0;
+}
+
+// fp32: a block of four normals = two packed date pairs per trip, as barrier_path<float>: one v_pk_fma_f32 for the pair's excursions
+// (its addend the pair's {yk, yk'} from two adjacent SGPRs) and one v_max3_f32.  CONT draws the four dates' uniforms from one raw
+// Philox block and adds per pair: two v_log_f32 and one packed multiply (shared by the mirrored path), then per direction a packed
+// subtract, a packed fma (the radicand), two v_sqrt_f32 and two packed adds.
+template <bool ANTI, bool CONT, class Gen>
+__device__ __forceinline__ float lookback_path(Gen &gen, const LookbackArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two packed date pairs per block");
+    const int n = o.n_dates;
+    // sbx in a vector register pair for the whole path: the packed fma's ONE scalar operand is the pair's {yk, yk'}
+    f2 sbx = bcast(o.sbx);
+    asm("" : "+v"(sbx));
+    [[maybe_unused]] const f2 e2 = bcast(o.e2);
+    float W = 0, Y = -__builtin_inff(), Y_m = -__builtin_inff();
+    float yp = 0, yp_m = 0;                           // y_{j-1} of the last date seen
+    float z[NPB];
+    float u[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    auto side = [&](f2 y, f2 be, float &Y_, float &yp_) {
+        if (CONT) {
+            const f2 prev = {yp_, y.x};
+            const f2 d = y - prev;
+            const f2 rad = pk_fma(d, d, be);
+            const f2 M2 = (y + prev) + (f2){__builtin_amdgcn_sqrtf(rad.x), __builtin_amdgcn_sqrtf(rad.y)};
+            Y_ = __builtin_fmaxf(__builtin_fmaxf(Y_, M2.x), M2.y);
+        } else {
+            Y_ = __builtin_fmaxf(__builtin_fmaxf(Y_, y.x), y.y);
+        }
+        yp_ = y.y;
+    };
+    auto pair = [&](int j, float z0, float z1, float u0, float u1) {
+        const f2 Wp = {W + z0, (W + z0) + z1};
+        W = Wp.y;
+        const f2 yk = {o.yk[j], o.yk[j + 1]};
+        f2 be = {0.0f, 0.0f};
+        if (CONT)
+            be = (f2){__builtin_amdgcn_logf(u0), __builtin_amdgcn_logf(u1)} * e2;
+        side(pk_fma(Wp, sbx, yk), be, Y, yp);
+        if (ANTI)
+            side(pk_fma(-Wp, sbx, yk), be, Y_m, yp_m);
+    };
+    auto single = [&](float y, float be, float &Y_, float &yp_) {
+        if (CONT) {
+            const float d = y - yp_;
+            Y_ = __builtin_fmaxf(Y_, (y + yp_) + __builtin_amdgcn_sqrtf(__builtin_fmaf(d, d, be)));
+        } else {
+            Y_ = __builtin_fmaxf(Y_, y);
+        }
+        yp_ = y;
+    };
+    int j0 = 0;
+    for (; j0 + NPB <= n; j0 += NPB) {
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 8u /*MC_DOMAIN_LOOKBACK*/, z);
+        if (CONT)
+            gen.uniforms(w, c0, (uint32_t)(j0 / NPB), 9u /*MC_DOMAIN_LOOKBACK_BRIDGE*/, u);
+        pair(j0, z[0], z[1], u[0], u[1]);
+        pair(j0 + 2, z[2], z[3], u[2], u[3]);
+    }
+    if (j0 < n) {   // wave-uniform: one to three dates left
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 8u /*MC_DOMAIN_LOOKBACK*/, z);
+        if (CONT)
+            gen.uniforms(w, c0, (uint32_t)(j0 / NPB), 9u /*MC_DOMAIN_LOOKBACK_BRIDGE*/, u);
+        if (j0 + 2 <= n) {
+            pair(j0, z[0], z[1], u[0], u[1]);
+            j0 += 2;
+        }
+        if (j0 < n) {
+            W += j0 & 2 ? z[2] : z[0];
+            const float yk = o.yk[j0];
+            const float be = CONT ? o.e2 * __builtin_amdgcn_logf(j0 & 2 ? u[2] : u[0]) : 0.0f;
+            single(__builtin_fmaf(W, o.sbx, yk), be, Y, yp);
+            if (ANTI)
+                single(__builtin_fmaf(-W, o.sbx, yk), be, Y_m, yp_m);
+        }
+    }
+    float val = lookback_value(Y, yp, o);
+    if (ANTI)
+        val = 0.5f * (val + lookback_value(Y_m, yp_m, o));
+    return val;
+}
+
+// max(a, b) of two doubles that are never signalling NaNs, as ONE v_max_f64 (min_f64's twin: hipcc puts a canonicalising
+// instruction in front of the running maximum's __builtin_fmax on every date)
+__device__ __forceinline__ double max_f64(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// c - a * b with c read from its SGPR pair: fma_scalar_addend on the mirrored path, the sign as the instruction's operand modifier
+// (a second register pair holding -b is what puts the fp64 antithetic continuous form over 128 vector registers)
+__device__ __forceinline__ double fnma_scalar_addend(double a, double b, double c)
+{
+    double r;
+    asm("v_fma_f64 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+
+// fp64: barrier_path<double>'s loop (Box-Muller pairs through the generator's pair cursor, four pairs per trip, then one): per
+// date one add, one v_fma_f64 with yk_j from its SGPR pair and one v_max_f64.  CONT: a pair of dates draws its two uniforms from
+// one raw Philox block, E_j by the table-driven -2 ln u of the normals, and per direction a subtract, the radicand's fma, sqrt_pos
+// and two adds.
+template <bool ANTI, bool CONT, class Gen>
+__device__ __forceinline__ double lookback_path(Gen &gen, const LookbackArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.n_dates;
+    double W = 0, Y = -__builtin_inf(), Y_m = -__builtin_inf(), yp = 0, yp_m = 0;
+    const double sbx_v = to_vgpr(o.sbx);
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto side = [&](double y, double E, double &Y_, double &yp_) {
+        if (CONT) {
+            const double d = y - yp_;
+            Y_ = max_f64(Y_, (y + yp_) + sqrt_pos(__builtin_fma(d, d, E)));
+        } else {
+            Y_ = max_f64(Y_, y);
+        }
+        yp_ = y;
+    };
+    auto date = [&](int j, double z, double E) {
+        W += z;
+        const double yk = o.yk[j];
+        side(fma_scalar_addend(W, sbx_v, yk), E, Y, yp);
+        if (ANTI)
+            side(fnma_scalar_addend(W, sbx_v, yk), E, Y_m, yp_m);
+    };
+    auto bridge = [&](uint32_t blk, double &E0, double &E1) {   // the two dates 2 blk, 2 blk + 1
+        E0 = E1 = 0.0;
+        if (CONT) {
+            double u[2];
+            gen.uniforms(w, c0, blk, 9u /*MC_DOMAIN_LOOKBACK_BRIDGE*/, u);
+            E0 = neg2log_unit_tab(u[0], K), E1 = neg2log_unit_tab(u[1], K);
+        }
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 8 <= n; j += 8) {
+            uint32_t blk = (uint32_t)(j >> 3);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // a pair's generator calls start after the running maximum of the pair before it: barrier_path<double>'s tie
+                if (k)
+                    asm("" : "+v"(Y), "+s"(blk));
+                double z0, z1, E0, E1;
+                gen.pair(w, c0, 8u /*MC_DOMAIN_LOOKBACK*/, (blk << 2) | k, carry, z0, z1);
+                // ... and the pair's uniforms after its normals (the same tie): overlapped, the two generator calls and the mirrored
+                // path's state need 131 vector registers, three waves per SIMD instead of four
+                uint32_t ub = (blk << 2) | k;
+                if (CONT)
+                    asm("" : "+v"(z1), "+s"(ub));
+                bridge(ub, E0, E1);
+                date(j + 2 * (int)k, z0, E0);
+                date(j + 2 * (int)k + 1, z1, E1);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; j += 2) {
+        double z0, z1, E0, E1;
+        gen.pair(w, c0, 8u /*MC_DOMAIN_LOOKBACK*/, (uint32_t)(j >> 1), carry, z0, z1);
+        bridge((uint32_t)(j >> 1), E0, E1);
+        date(j, z0, E0);
+        if (j + 1 < n)   // wave-uniform
+            date(j + 1, z1, E1);
+    }
+    gen.pairs_done((uint32_t)((n + 1) >> 1));
+    double val = lookback_value(Y, yp, o);
+    if (ANTI)
+        val = 0.5 * (val + lookback_value(Y_m, yp_m, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths: barrier_kernel's frame
+template <class Real, bool ANTI, bool CONT, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void lookback_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const LookbackArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = lookback_path<ANTI, CONT>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // European call under the Heston stochastic-volatility model, full-truncation Euler in log space on m equal steps (the model
 // is stated in mc_mi355x.h).  Not in the reference.  The first walk here whose step is non-linear in its state: besides the
 // normals a lane carries the variance V and two running sums, because
@@ -3161,6 +3399,20 @@ __global__ __launch_bounds__(GROUP) void normals_kernel(const Work w, uint32_t b
         for (int j = 0; j < NPB; ++j)
             out[(uint64_t)i * NPB + j] = z[j];
     }
+}
+
+// Raw words dump (the tests rebuild the bridge uniforms from them): Philox blocks first_block .. first_block + n_blocks - 1 of
+// each unit, four words per block, unit-major: out[(i * n_blocks + b) * 4 + k].
+__global__ __launch_bounds__(GROUP) void words_kernel(const Work w, uint32_t domain, uint32_t first_block, uint32_t n_blocks, uint32_t *__restrict__ out)
+{
+    const uint32_t stride = gridDim.x * GROUP;
+    GenPhilox gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride)
+        for (uint32_t b = 0; b < n_blocks; ++b) {
+            const u32x4 r = gen.words(w, w.unit_lo + i, first_block + b, domain);
+            uint32_t *p = out + ((uint64_t)i * n_blocks + b) * 4u;
+            p[0] = r.x, p[1] = r.y, p[2] = r.z, p[3] = r.w;
+        }
 }
 
 }  // namespace mc

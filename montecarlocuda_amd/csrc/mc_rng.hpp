@@ -249,6 +249,7 @@ typedef float f2 __attribute__((ext_vector_type(2)));  // one VGPR pair: v_pk_{f
 //   words(w, unit_lo, block, domain)                    the block's four raw words (word-level kernels: the packed-fp32
 //                                                       kernels build two paths' normals from words themselves);
 //                                                       absent when `external`
+//   uniforms(w, unit_lo, block, domain, Real (&u)[..])  GenPhilox only: the uniforms of one raw block (4 in f32, 2 in f64)
 //   external                                            normals come from memory, there are no words
 //
 // GenPhilox: the engine's generator.  Stateless: block (unit, block, domain) is a pure function of the counter.
@@ -289,6 +290,19 @@ struct GenPhilox {
     __device__ __forceinline__ void normals(const Work &w, uint32_t unit_lo, uint32_t block, uint32_t domain, float (&z)[4])
     {
         words_to_normals(words(w, unit_lo, block, domain), z);
+    }
+    // UNIFORMS, the second kind of draw (the lookback call's Brownian-bridge maxima, in a domain of their own): RAW Philox block
+    // `block` of the unit, no three-block grouping.  fp32: one word per uniform, u in (0, 1]; fp64: words (0, 1) and (2, 3) as
+    // (lo, hi) of a 52-bit uniform strictly inside (0, 1).  Philox only: the products that draw uniforms refuse the other generators.
+    __device__ __forceinline__ void uniforms(const Work &w, uint32_t unit_lo, uint32_t block, uint32_t domain, float (&u)[4])
+    {
+        const u32x4 r = words(w, unit_lo, block, domain);
+        u[0] = u01_f32(r.x), u[1] = u01_f32(r.y), u[2] = u01_f32(r.z), u[3] = u01_f32(r.w);
+    }
+    __device__ __forceinline__ void uniforms(const Work &w, uint32_t unit_lo, uint32_t block, uint32_t domain, double (&u)[2])
+    {
+        const u32x4 r = words(w, unit_lo, block, domain);
+        u[0] = u01_f64(r.x, r.y), u[1] = u01_f64(r.z, r.w);
     }
     // fp64: block b of the stream = Philox blocks 3b, 3b + 1, 3b + 2 (a kernel that uses only some of the eight normals
     // pays only for the Philox blocks those need: the rest is dead code after unrolling)

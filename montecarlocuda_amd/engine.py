@@ -121,6 +121,16 @@ def _as_barrier(X, o, barrier=None, n_dates=None, kind=None, monitoring=None) ->
     return _lib.BARRIER[X](_as_option(X, o), float(barrier), int(n_dates), kind, monitoring)
 
 
+def _as_lookback(X, o, n_dates=None, kind=None, monitoring=None) -> C.Structure:
+    """mc_lookback_*: an option (OptionData or dict) with the contract's fields, or a dict that carries "n_dates" and optionally "kind" /
+    "monitoring" itself.  kind and monitoring: the names of _lib.LOOKBACK_TYPES / _lib.MONITORING, or the header's integers."""
+    if n_dates is None:
+        n_dates, kind, monitoring = o["n_dates"], o.get("kind", "floating-call"), o.get("monitoring", "discrete")
+    kind = _lib.LOOKBACK_TYPES[kind] if isinstance(kind, str) else int(kind)
+    monitoring = _lib.MONITORING[monitoring] if isinstance(monitoring, str) else int(monitoring)
+    return _lib.LOOKBACK[X](_as_option(X, o), int(n_dates), kind, monitoring)
+
+
 def _as_heston(X, o, model=None, n_steps=None) -> C.Structure:
     """mc_heston_*: an option (OptionData or dict; its v is ignored) with the model {v0, kappa, theta, xi, rho} and n_steps, or a
     dict that carries the model's five fields and "n_steps" itself."""
@@ -395,6 +405,14 @@ class Engine:
         the dates: unbiased for the continuously monitored price, barrier_closed_form).  Honours set_antithetic."""
         return self._run("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
 
+    def lookback(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
+                 monitoring="discrete") -> Estimate:
+        """Lookback option on n_dates equally spaced dates (mc_lookback_run_*).  kind: "floating-call", "floating-put", "fixed-call",
+        "fixed-put" (opt's k is ignored by the floating types); monitoring: "discrete" (the extremum over the dates) or "continuous"
+        (Brownian-bridge maxima between the dates: unbiased for the continuously monitored price, lookback_closed_form).  Honours
+        set_antithetic."""
+        return self._run("lookback", precision, _as_lookback(precision, opt, n_dates, kind, monitoring), seed, first_path, n_paths)
+
     def heston(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
         """European call under the Heston model, full-truncation Euler on n_steps equal steps (mc_heston_run_*).  model: a dict
         with v0, kappa, theta, xi, rho; opt's v is ignored.  Honours set_antithetic; biased by the scheme against
@@ -434,6 +452,8 @@ class Engine:
             return _as_heston(precision, inputs), None
         if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
             return _as_heston_path(precision, inputs), None
+        if prod == "lookback":   # inputs: the option's fields plus "n_dates" and optionally "kind", "monitoring"
+            return _as_lookback(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
             return _as_barrier(precision, inputs), None
         return _as_cva(precision, inputs), None
@@ -462,6 +482,10 @@ class Engine:
                       monitoring="discrete"):
         return self._paths("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
 
+    def lookback_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
+                       monitoring="discrete"):
+        return self._paths("lookback", precision, _as_lookback(precision, opt, n_dates, kind, monitoring), seed, first_path, n_paths)
+
     def heston_paths(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
 
@@ -479,6 +503,13 @@ class Engine:
         check(getattr(lib(), f"mc_normals_{precision}")(self._ctx, seed, domain, first_unit, n_units, block,
                                                          out.ctypes.data_as(C.POINTER(_lib.CT[precision]))))
         return out.reshape(n_units, npb)
+
+    def words(self, seed, domain, first_unit, n_units, first_block=0, n_blocks=1):
+        """The raw Philox words of blocks first_block .. first_block + n_blocks - 1 of each unit: (n_units, n_blocks, 4) uint32
+        (test hook, mc_words)."""
+        out = np.empty((n_units, n_blocks, 4), dtype=np.uint32)
+        check(lib().mc_words(self._ctx, seed, domain, first_unit, n_units, first_block, n_blocks, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     # ---- compatibility mode: the reference's launch geometry and per-thread XORWOW streams (mc_*_run_grid_*) ----
     def run_grid(self, prod, inputs, num_blocks, num_threads, paths_per_block, precision="f64") -> Estimate:
@@ -580,6 +611,14 @@ def barrier_closed_form(opt, barrier, kind="up-and-out", precision="f64"):
     """Discounted Reiner-Rubinstein price of the continuously monitored single-barrier call (no dividend, no rebate; fp64)."""
     p = C.c_double()
     check(getattr(lib(), f"mc_barrier_closed_form_{precision}")(C.byref(_as_barrier(precision, opt, barrier, 1, kind, "continuous")), C.byref(p)))
+    return p.value
+
+
+def lookback_closed_form(opt, kind="floating-call", precision="f64"):
+    """Discounted price at inception of the continuously monitored lookback option (Goldman-Sosin-Gatto for the floating strikes,
+    Conze-Viswanathan for the fixed ones; no dividend; fp64)."""
+    p = C.c_double()
+    check(getattr(lib(), f"mc_lookback_closed_form_{precision}")(C.byref(_as_lookback(precision, opt, 1, kind, "continuous")), C.byref(p)))
     return p.value
 
 
