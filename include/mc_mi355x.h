@@ -73,6 +73,8 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_HESTON_PATH 7u
 #define MC_DOMAIN_LOOKBACK 8u
 #define MC_DOMAIN_LOOKBACK_BRIDGE 9u /* the lookback call's uniforms: raw Philox blocks, see mc_lookback_run_* */
+#define MC_DOMAIN_MERTON 10u
+#define MC_DOMAIN_MERTON_JUMPS 11u /* the jump-diffusion's Poisson counts: raw Philox blocks, see mc_merton_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -143,6 +145,17 @@ typedef struct { mc_option_f64 option; double v0, kappa, theta, xi, rho; int n_s
 enum { MC_HESTON_PATH_ASIAN = 0, MC_HESTON_PATH_BARRIER = 1 };
 typedef struct { mc_heston_f32 heston; int steps_per_date, payoff, barrier_type; float barrier; } mc_heston_path_f32;
 typedef struct { mc_heston_f64 heston; int steps_per_date, payoff, barrier_type; double barrier; } mc_heston_path_f64;
+
+/* Calls under Merton's jump-diffusion on n_dates equally spaced dates (see mc_merton_run_*): the European call, the
+ * arithmetic-average call and the single-barrier call monitored on the dates.  Not in the reference.  lambda is the jump
+ * intensity per year, ln J ~ N(mu_j, delta^2) the jump size.  barrier_type is one of MC_BARRIER_*; barrier and barrier_type are
+ * ignored by the other two payoffs.  One table value per date (the Asian call's table, same cap, same rounding argument), then
+ * the Poisson thresholds and the per-count volatilities: at most MC_MAX_MERTON_JUMPS jumps per date. */
+#define MC_MAX_MERTON_DATES 4096
+#define MC_MAX_MERTON_JUMPS 40
+enum { MC_MERTON_EUROPEAN = 0, MC_MERTON_ASIAN = 1, MC_MERTON_BARRIER = 2 };
+typedef struct { mc_option_f32 option; float lambda, mu_j, delta; int n_dates, payoff, barrier_type; float barrier; } mc_merton_f32;
+typedef struct { mc_option_f64 option; double lambda, mu_j, delta; int n_dates, payoff, barrier_type; double barrier; } mc_merton_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -525,6 +538,65 @@ int mc_heston_path_launch_f64(mc_context *ctx, const mc_heston_path_f64 *opt, ui
                               double *d_triple, void *stream);
 int mc_heston_path_paths_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
 int mc_heston_path_paths_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+
+/* ---- calls under Merton's jump-diffusion: European, Asian, discretely monitored barrier ----------------------
+ * dS/S = (r - lambda kappa) dt + v dW + (J - 1) dN,  N Poisson with rate lambda,  ln J ~ N(mu_j, delta^2),
+ * kappa = exp(mu_j + delta^2/2) - 1 (the compensator: e^{-rt} S is a martingale).  The first model here with a DISCONTINUOUS path.
+ * On m = n_dates equally spaced dates, dt = t/m, a = (r - lambda kappa - v^2/2) dt, bx = v sqrt(dt), date j draws a count
+ * N_j ~ Poisson(lambda dt) and ONE normal z_j: given N_j, the diffusion increment plus the N_j jumps is one normal with mean
+ * a + mu_j N_j and deviation s_{N_j}, s_n = sqrt(bx^2 + n delta^2).  So the walk is EXACT IN LAW at any n_dates:
+ *     C_j = N_1 + ... + N_j,   A_j = sum_{i<=j} s_{N_i} z_i,   x_j = ln S_j = ln s + j a + mu_j C_j + A_j.
+ * Per path, undiscounted:
+ *   MC_MERTON_EUROPEAN   (exp(x_m) - k)^+
+ *   MC_MERTON_ASIAN      ((1/m) sum_j exp(x_j) - k)^+
+ *   MC_MERTON_BARRIER    sgn = +1 (up) or -1 (down), d_j = sgn (ln barrier - x_j), P = [min_j d_j > 0] taken by a select;
+ *                        (c0 + c1 P)(exp(x_m) - k)^+, (c0, c1) = (0, 1) knock-out, (1, -1) knock-in.  Monitored ON THE DATES
+ *                        ONLY; a crossed knock-out is exactly 0.  (A jump breaks the Brownian-bridge argument: no continuous form.)
+ * mc_context_set_antithetic: the mean of the value at z and at -z on the SAME counts N_j (any coupling of the counts is
+ * unbiased; sharing them halves the count work, as the lookback's bridge draws are shared); A^-_j = -A_j exactly; n counts pairs.
+ * lambda = 0, delta = 0 and mu_j = 0 are valid; lambda = 0 is the constant-volatility product.  v = 0 is valid with any
+ * delta: s_0 = 0 is an exact 0 (a date without a jump then adds 0 z = 0, nothing divides by s_n).
+ * Stream: path p is unit p of MC_DOMAIN_MERTON, date j (1-based) draws entry (j - 1) % npb of block (j - 1) / npb: the Asian
+ * layout under its own domain word.  The counts come from RAW Philox blocks of the same unit in MC_DOMAIN_MERTON_JUMPS, the
+ * lookback's bridge layout: f32 date j takes the 32-bit word (j - 1) % 4 of block (j - 1) / 4; f64 date j takes words
+ * 2 ((j - 1) % 2) and 2 ((j - 1) % 2) + 1 of block (j - 1) / 2 as (lo, hi) of a 64-bit word.
+ * The count is an exact integer inversion of that word w, W = 32 or 64 bits, no float conversion on the device:
+ *     N = #{k < K : w >= T_k},   T_0 <= T_1 <= ... <= T_{K-1} < 2^W       (N = 0 iff w < T_0; K = 0: N = 0 always)
+ * with p = lambda dt (fp64), f_n = e^{-p} p^n / n! by f_n = f_{n-1} p / n and F_k = f_0 + ... + f_k, both in long double:
+ *     T_k = min(floor(F_k 2^W), 2^W - 1),
+ *     K   = the smallest k >= 0 with tail_k = sum_{n > k} f_n < 2^-(W+1)   (the tail summed from its small end, never as 1 - F_k),
+ * so a count above K has probability below 2^-(W+1): it is folded into N = K.  p = 0 gives K = 0.  K > MC_MAX_MERTON_JUMPS is
+ * refused (p <= 5 needs K = 25 at 32 and K = 37 at 64 bits; the cap is reached at p = 12.39 and p = 6.23).  |T_k / 2^W - F_k|
+ * <= 2^-W from the floor plus the rounding of F_k, a few 2^-64 in the x87 long double: within the documented 2^-W + 4 2^-53.
+ * mc_merton_thresholds_* writes T_0 ... T_{K-1} to out (room for MC_MAX_MERTON_JUMPS values) and K to *count; plain C, no GPU.
+ * mc_merton_closed_form_*: the discounted price of MC_MERTON_EUROPEAN (fp64; ignores n_dates, payoff and the barrier; usable
+ * without a GPU): Merton's series
+ *     sum_n e^{-l t} (l t)^n / n! BS(s, k, r_n, v_n, t),  l = lambda (1 + kappa), v_n^2 = v^2 + n delta^2 / t,
+ *     r_n = r - lambda kappa + n ln(1 + kappa) / t,
+ * BS the Black-Scholes call (Phi by erfc; v_n = 0: max(s - k e^{-r_n t}, 0)), summed until the Poisson weight left is below
+ * 1e-18.  Needs k > 0.  Within 1e-10 of a 30-digit quadrature of the characteristic function at s = 100 (measured: 2e-14 at most).
+ * Path ranges, the finish, call statistics, timing, arming and ordering as for the other products; several GPUs as for the
+ * Asian call.
+ * MC_ERR_INVALID before anything is enqueued: n_dates outside [1, MC_MAX_MERTON_DATES]; payoff out of range; s <= 0, t <= 0,
+ * v < 0, lambda < 0, delta < 0 or a non-finite input; for the barrier payoff what mc_barrier_run_* refuses (type, barrier <= 0,
+ * the spot on or beyond the barrier); more than MC_MAX_MERTON_JUMPS thresholds; drift, volatility and jumps that can put the
+ * exponent |ln s| + m (|a| + |mu_j| K + (bx + delta sqrt(K)) z_max) outside the device exponential's range.
+ * MC_ERR_UNSUPPORTED: the control variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a
+ * context set up for external normals or the launch geometry.  The context stays usable.  No puts, no continuous monitoring,
+ * no control variate, no Greeks, no book, no other jump law, no jumps on the Heston walk.
+ * mc_merton_paths_* returns the per-path values (undiscounted; n_paths <= 2^26). */
+int mc_merton_run_f32(mc_context *ctx, const mc_merton_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_merton_run_f64(mc_context *ctx, const mc_merton_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_merton_launch_f32(mc_context *ctx, const mc_merton_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                         double *d_triple, void *stream);
+int mc_merton_launch_f64(mc_context *ctx, const mc_merton_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                         double *d_triple, void *stream);
+int mc_merton_paths_f32(mc_context *ctx, const mc_merton_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_merton_paths_f64(mc_context *ctx, const mc_merton_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_merton_closed_form_f32(const mc_merton_f32 *opt, double *price);
+int mc_merton_closed_form_f64(const mc_merton_f64 *opt, double *price);
+int mc_merton_thresholds_f32(const mc_merton_f32 *opt, uint64_t *out, int *count);
+int mc_merton_thresholds_f64(const mc_merton_f64 *opt, uint64_t *out, int *count);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

@@ -21,6 +21,10 @@ MAX_ASIAN_DATES = 4096   # MC_MAX_ASIAN_DATES
 MAX_BARRIER_DATES = 4096   # MC_MAX_BARRIER_DATES
 MAX_HESTON_STEPS = 4096   # MC_MAX_HESTON_STEPS
 MAX_LOOKBACK_DATES = 4096   # MC_MAX_LOOKBACK_DATES
+DOMAIN_MERTON, DOMAIN_MERTON_JUMPS = 10, 11   # normals; the Poisson counts (raw Philox blocks)
+MAX_MERTON_DATES = 4096   # MC_MAX_MERTON_DATES
+MAX_MERTON_JUMPS = 40   # MC_MAX_MERTON_JUMPS
+MERTON_PAYOFFS = {"european": 0, "asian": 1, "barrier": 2}   # MC_MERTON_EUROPEAN, MC_MERTON_ASIAN, MC_MERTON_BARRIER
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
 LOOKBACK_TYPES = {"floating-call": 0, "floating-put": 1, "fixed-call": 2, "fixed-put": 3}   # MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
@@ -88,6 +92,16 @@ class LookbackF64(C.Structure):   # mc_lookback_f64
     _fields_ = [("option", OptionF64), ("n_dates", C.c_int), ("type", C.c_int), ("monitoring", C.c_int)]
 
 
+class MertonF32(C.Structure):   # mc_merton_f32
+    _fields_ = [("option", OptionF32), ("lambda_", C.c_float), ("mu_j", C.c_float), ("delta", C.c_float), ("n_dates", C.c_int), ("payoff", C.c_int),
+                ("barrier_type", C.c_int), ("barrier", C.c_float)]
+
+
+class MertonF64(C.Structure):   # mc_merton_f64
+    _fields_ = [("option", OptionF64), ("lambda_", C.c_double), ("mu_j", C.c_double), ("delta", C.c_double), ("n_dates", C.c_int), ("payoff", C.c_int),
+                ("barrier_type", C.c_int), ("barrier", C.c_double)]
+
+
 class HestonF32(C.Structure):   # mc_heston_f32
     _fields_ = [("option", OptionF32), ("v0", C.c_float), ("kappa", C.c_float), ("theta", C.c_float), ("xi", C.c_float), ("rho", C.c_float),
                 ("n_steps", C.c_int)]
@@ -145,6 +159,7 @@ ASIAN = {"f32": AsianF32, "f64": AsianF64}
 BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
 LOOKBACK = {"f32": LookbackF32, "f64": LookbackF64}
 HESTON = {"f32": HestonF32, "f64": HestonF64}
+MERTON = {"f32": MertonF32, "f64": MertonF64}
 HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
 
@@ -168,6 +183,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
+    EXPORTS += [f"mc_merton_run_{_x}", f"mc_merton_launch_{_x}", f"mc_merton_paths_{_x}", f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}"]
     EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
     EXPORTS += [f"mc_heston_path_run_{_x}", f"mc_heston_path_launch_{_x}", f"mc_heston_path_paths_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
@@ -255,6 +271,11 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_lookback_run_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_lookback_paths_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, RP]
         getattr(L, f"mc_lookback_closed_form_{X}").argtypes = [C.POINTER(LOOKBACK[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_merton_launch_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_merton_run_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_merton_paths_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_merton_closed_form_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_merton_thresholds_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         getattr(L, f"mc_heston_launch_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]

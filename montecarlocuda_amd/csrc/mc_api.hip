@@ -84,7 +84,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a jump-diffusion call's dates, thresholds and s_n, a generic basket's folded constants, a basket's Greeks table
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // generator: Philox (counter-based, stateless) or XORWOW (one sequence per lane: mc_rng.hpp GenXorwow)
@@ -2391,6 +2391,113 @@ static int lookback_enqueue(mc_context *c, const typename LookbackIn<Real>::type
         });
 }
 
+// ---------------------------------------------------------------------------------------
+// Calls under Merton's jump-diffusion (European, Asian, discretely monitored barrier): merton_kernel, one lane per path
+// ---------------------------------------------------------------------------------------
+template <class Real> struct MertonIn;
+template <> struct MertonIn<float> { using type = mc_merton_f32; };
+template <> struct MertonIn<double> { using type = mc_merton_f64; };
+static int merton_thresholds(const mc_merton_f32 &o, uint64_t *out, int *count) { return mc_merton_thresholds_f32(&o, out, count); }
+static int merton_thresholds(const mc_merton_f64 &o, uint64_t *out, int *count) { return mc_merton_thresholds_f64(&o, out, count); }
+
+// The checks (mc_merton_thresholds_* runs mc_merton_check_* and the cap on K), the constants folded in fp64 and rounded once, and
+// the table in the context's buffer, cached by content, uploaded only when the inputs change:
+//   n_dates values   xk_j = ln S0 + j a (exponent units), or for the barrier payoff dk_j = sgn (ln B - ln S0 - j a) (natural log)
+//   K thresholds     T_0 ... T_{K-1}, as integers of the width of Real
+//   K + 1 values     s_n = sqrt(bx^2 + n delta^2), n = 0 ... K, in the units of the first part
+template <class Real>
+static int merton_table_ready(mc_context *c, const typename MertonIn<Real>::type *v, hipStream_t st, MertonArgs<Real> &args)
+{
+    using Word = typename MertonWord<Real>::type;
+    static_assert(sizeof(Word) == sizeof(Real), "thresholds travel in the table's own element size");
+    const auto &o = v->option;
+    uint64_t thr[MC_MAX_MERTON_JUMPS];
+    int K = 0;
+    if (int rc = merton_thresholds(*v, thr, &K)) return rc;
+    const bool barrier = v->payoff == MC_MERTON_BARRIER;
+    const double sc = exp_scale<Real>(), unit = barrier ? 1.0 : sc;
+    const double m = (double)v->n_dates, dt = (double)o.t / m;
+    const double lambda = (double)v->lambda, mu = (double)v->mu_j, delta = (double)v->delta;
+    const double kappa = std::expm1(mu + 0.5 * delta * delta);
+    const double a = ((double)o.r - lambda * kappa - 0.5 * (double)o.v * (double)o.v) * dt, bx = (double)o.v * std::sqrt(dt), ln_s0 = std::log((double)o.s);
+    const double sgn = barrier && v->barrier_type > MC_BARRIER_UP_IN ? -1.0 : 1.0, gap = barrier ? std::log((double)v->barrier) - ln_s0 : 0.0;
+    // as for the Asian call: only the hard limit of the device's exp is enforced; a date moves the log price by at most
+    // |a| + |mu_j| K + s_K z_max, s_K <= bx + delta sqrt(K)
+    if (!(std::fabs(ln_s0) + std::fabs(gap) + m * (std::fabs(a) + std::fabs(mu) * (double)K + (bx + delta * std::sqrt((double)K)) * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+        return fail(MC_ERR_INVALID, "merton: drift, volatility and jumps put the simulated spot outside the range of a double");
+    static thread_local std::vector<Real> tab;
+    const size_t nd = (size_t)v->n_dates;
+    tab.resize(nd + (size_t)K + (size_t)K + 1);
+    for (int j = 1; j <= v->n_dates; ++j)
+        tab[(size_t)j - 1] = barrier ? (Real)(sgn * (gap - (double)j * a)) : (Real)((ln_s0 + (double)j * a) * sc);
+    for (int k = 0; k < K; ++k) {
+        const Word t = (Word)thr[k];
+        memcpy(&tab[nd + (size_t)k], &t, sizeof t);
+    }
+    for (int k = 0; k <= K; ++k)
+        tab[nd + (size_t)K + (size_t)k] = (Real)(std::sqrt(bx * bx + (double)k * delta * delta) * unit);
+    if (int rc = c->table.upload(c, st, table_key(tab, barrier ? 'N' : 'M'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    const bool in = barrier && (v->barrier_type == MC_BARRIER_UP_IN || v->barrier_type == MC_BARRIER_DOWN_IN);
+    args.xk = (const Real *)c->table.d;
+    args.thr = (const Word *)(args.xk + nd);
+    args.sn = args.xk + nd + (size_t)K;
+    args.n_dates = v->n_dates;
+    args.n_thr = K;
+    args.thr0 = K > 0 ? (Word)thr[0] : (Word)0;
+    args.s0 = tab[nd + (size_t)K];
+    args.emu = (Real)(mu * sc);
+    args.dmu = (Real)(-sgn * mu);
+    args.dsg = (Real)(-sgn);
+    args.xT = (Real)((ln_s0 + m * a) * sc);
+    args.ex = (Real)sc;
+    args.strike = o.k;
+    args.inv_m = (Real)(1.0 / m);
+    args.c0 = in ? (Real)1 : (Real)0;
+    args.c1 = in ? (Real)-1 : (Real)1;
+    return MC_OK;
+}
+
+template <class Real>
+static int merton_enqueue(mc_context *c, const typename MertonIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                          double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "merton: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "merton: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "merton: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_UNSUPPORTED, "merton: no control variate");
+    uint64_t thr[MC_MAX_MERTON_JUMPS];
+    int K = 0;
+    if (int rc = merton_thresholds(*v, thr, &K)) return rc;   // the input checks and the cap, before the call begins
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    MertonArgs<Real> args;
+    if (int rc = merton_table_ready<Real>(c, v, st, args)) return rc;
+    const int payoff = v->payoff;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) {
+                if (payoff == MC_MERTON_ASIAN)        launch_sim(prof, merton_kernel<Real, true, MERTON_ASIAN>, g, st, t, args, w, dst);
+                else if (payoff == MC_MERTON_BARRIER) launch_sim(prof, merton_kernel<Real, true, MERTON_BARRIER>, g, st, t, args, w, dst);
+                else                                  launch_sim(prof, merton_kernel<Real, true, MERTON_EUROPEAN>, g, st, t, args, w, dst);
+            } else {
+                if (payoff == MC_MERTON_ASIAN)        launch_sim(prof, merton_kernel<Real, false, MERTON_ASIAN>, g, st, t, args, w, dst);
+                else if (payoff == MC_MERTON_BARRIER) launch_sim(prof, merton_kernel<Real, false, MERTON_BARRIER>, g, st, t, args, w, dst);
+                else                                  launch_sim(prof, merton_kernel<Real, false, MERTON_EUROPEAN>, g, st, t, args, w, dst);
+            }
+            return MC_OK;
+        });
+}
+
 template <class Real> struct HestonIn;
 template <> struct HestonIn<float> { using type = mc_heston_f32; };
 template <> struct HestonIn<double> { using type = mc_heston_f64; };
@@ -3413,6 +3520,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return lookback_enqueue<Real>(c, o, seed, first, n, t, st, d);                                   \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_merton_launch_##X(mc_context *c, const mc_merton_##X *o, uint64_t seed, uint64_t first,\
+                                        uint64_t n, double *d_triple, void *stream)                          \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return merton_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);        \
+    }                                                                                                        \
+    extern "C" int mc_merton_run_##X(mc_context *c, const mc_merton_##X *o, uint64_t seed, uint64_t first,   \
+                                     uint64_t n, mc_result *out)                                             \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->option.r * (double)o->option.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return merton_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                               \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_merton_paths_##X(mc_context *c, const mc_merton_##X *o, uint64_t seed, uint64_t first, \
+                                       uint64_t n, Real *h_out)                                              \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return merton_enqueue<Real>(c, o, seed, first, n, t, st, d);                                     \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_heston_launch_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first,\

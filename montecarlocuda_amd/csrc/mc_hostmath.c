@@ -12,6 +12,8 @@
  *   mc_asian_control_mean_*  closed-form mean of the geometric-average control variate of the Asian call
  *   mc_barrier_closed_form_* Reiner-Rubinstein price of the continuously monitored single-barrier call
  *   mc_lookback_closed_form_* Goldman-Sosin-Gatto / Conze-Viswanathan prices of the continuously monitored lookbacks
+ *   mc_merton_closed_form_*  Merton's series for the European call under the jump-diffusion; mc_merton_thresholds_* the integer
+ *                            Poisson thresholds of its count draw
  *   mc_heston_closed_form_*  exact price of the European call under the Heston model (Gauss-Legendre quadrature)
  *   mc_last_error / mc_internal_fail   the per-thread error text of whichever library this object is linked into
  */
@@ -124,6 +126,8 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define BARRIER mc_barrier_f32
 #define LOOKBACK mc_lookback_f32
 #define HESTON mc_heston_f32
+#define MERTON mc_merton_f32
+#define MERTON_BITS 32
 #include "mc_hostmath_impl.h"
 #undef REAL
 #undef SQRT_R
@@ -133,6 +137,8 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef BARRIER
 #undef LOOKBACK
 #undef HESTON
+#undef MERTON
+#undef MERTON_BITS
 
 #define REAL double
 #define SQRT_R sqrt
@@ -142,6 +148,8 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define BARRIER mc_barrier_f64
 #define LOOKBACK mc_lookback_f64
 #define HESTON mc_heston_f64
+#define MERTON mc_merton_f64
+#define MERTON_BITS 64
 #include "mc_hostmath_impl.h"
 #undef REAL
 #undef SQRT_R
@@ -151,3 +159,5 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef BARRIER
 #undef LOOKBACK
 #undef HESTON
+#undef MERTON
+#undef MERTON_BITS

@@ -284,3 +284,101 @@ int FN(mc_heston_closed_form)(const HESTON *o, double *price)
     *price = c;
     return MC_OK;
 }
+
+/* The inputs every jump-diffusion entry point refuses (see mc_mi355x.h); the threshold cap is mc_merton_thresholds_*'s.  Internal
+ * (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_merton_check)(const MERTON *o)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    const double lambda = (double)o->lambda, mu = (double)o->mu_j, delta = (double)o->delta;
+    if (o->n_dates < 1 || o->n_dates > MC_MAX_MERTON_DATES)
+        return mc_internal_fail(MC_ERR_INVALID, "merton: n_dates=%d outside [1, %d]", o->n_dates, MC_MAX_MERTON_DATES);
+    if (o->payoff < MC_MERTON_EUROPEAN || o->payoff > MC_MERTON_BARRIER)
+        return mc_internal_fail(MC_ERR_INVALID, "merton: payoff=%d is none of MC_MERTON_EUROPEAN, MC_MERTON_ASIAN, MC_MERTON_BARRIER", o->payoff);
+    if (!isfinite(s) || !isfinite(k) || !isfinite(r) || !isfinite(v) || !isfinite(t) || !isfinite(lambda) || !isfinite(mu) || !isfinite(delta))
+        return mc_internal_fail(MC_ERR_INVALID, "merton: need finite s, k, r, v, t, lambda, mu_j, delta");
+    if (!(s > 0) || !(t > 0) || !(v >= 0) || !(lambda >= 0) || !(delta >= 0))
+        return mc_internal_fail(MC_ERR_INVALID, "merton: need s>0, t>0, v>=0, lambda>=0, delta>=0");
+    if (o->payoff == MC_MERTON_BARRIER) {
+        BARRIER b = {.option = o->option, .barrier = o->barrier, .n_dates = o->n_dates, .type = o->barrier_type, .monitoring = MC_MONITOR_DISCRETE};
+        return FN(mc_barrier_check)(&b, 0);
+    }
+    return MC_OK;
+}
+
+/* The integer thresholds of the Poisson(lambda dt) count drawn from a MERTON_BITS-bit word (the rule is stated in mc_mi355x.h). */
+int FN(mc_merton_thresholds)(const MERTON *o, uint64_t *out, int *count)
+{
+    if (!o || !out || !count)
+        return mc_internal_fail(MC_ERR_INVALID, "merton thresholds: NULL argument");
+    int rc = FN(mc_merton_check)(o);
+    if (rc != MC_OK)
+        return rc;
+    enum { TERMS = 256 };   /* p <= MC_MAX_MERTON_JUMPS here: f_256 is below 1e-130 of the mode */
+    const double p = (double)o->lambda * ((double)o->option.t / (double)o->n_dates);
+    if (!(p <= (double)MC_MAX_MERTON_JUMPS))   /* the mean alone is beyond the cap */
+        return mc_internal_fail(MC_ERR_INVALID, "merton: lambda dt = %g needs more than %d Poisson thresholds", p, MC_MAX_MERTON_JUMPS);
+    long double f[TERMS], tail[TERMS];   /* tail[k] = sum_{n > k} f_n, summed from the small end */
+    f[0] = expl(-(long double)p);
+    for (int n = 1; n < TERMS; ++n)
+        f[n] = f[n - 1] * (long double)p / (long double)n;
+    tail[TERMS - 1] = 0.0L;
+    for (int n = TERMS - 1; n > 0; --n)
+        tail[n - 1] = tail[n] + f[n];
+    const long double eps = ldexpl(1.0L, -(MERTON_BITS + 1)), top = ldexpl(1.0L, MERTON_BITS);
+    int K = 0;
+    while (K < TERMS - 1 && !(tail[K] < eps))
+        ++K;
+    if (K > MC_MAX_MERTON_JUMPS)
+        return mc_internal_fail(MC_ERR_INVALID, "merton: lambda dt = %g needs %d Poisson thresholds, more than %d", p, K, MC_MAX_MERTON_JUMPS);
+    const uint64_t last = MERTON_BITS == 64 ? UINT64_MAX : (uint64_t)0xFFFFFFFFu;
+    long double F = 0.0L;
+    for (int k = 0; k < K; ++k) {
+        F += f[k];
+        const long double x = floorl(F * top);
+        out[k] = x >= top ? last : (uint64_t)x;
+        if (k && out[k] < out[k - 1])   /* cannot happen (F is a sum of non-negative terms); kept as the contract */
+            out[k] = out[k - 1];
+    }
+    *count = K;
+    return MC_OK;
+}
+
+/* Discounted price of the European call under Merton's jump-diffusion: the Poisson-weighted series of Black-Scholes prices
+ * stated in mc_mi355x.h, fp64, Phi by erfc. */
+int FN(mc_merton_closed_form)(const MERTON *o, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "merton closed form: NULL argument");
+    MERTON one = *o;
+    one.n_dates = 1, one.payoff = MC_MERTON_EUROPEAN;   /* both ignored here */
+    int rc = FN(mc_merton_check)(&one);
+    if (rc != MC_OK)
+        return rc;
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    const double lambda = (double)o->lambda, mu = (double)o->mu_j, delta = (double)o->delta;
+    if (!(k > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "merton closed form: needs k > 0");
+    const double kappa = expm1(mu + 0.5 * delta * delta), g = mu + 0.5 * delta * delta;   /* g = ln(1 + kappa) */
+    const double lt = lambda * (1.0 + kappa) * t;
+    if (!(lt < 700.0))   /* e^{-lt} must not underflow */
+        return mc_internal_fail(MC_ERR_INVALID, "merton closed form: lambda (1 + kappa) t = %g is beyond the series' range", lt);
+    double w = exp(-lt), sum = 0.0;   /* the Poisson weight of n */
+    for (int n = 0; n < 100000; ++n) {
+        const double rn = r - lambda * kappa + (double)n * g / t, sd = sqrt(v * v * t + (double)n * delta * delta), kd = k * exp(-rn * t);
+        double bs;
+        if (!(sd > 0)) {
+            bs = fmax(s - kd, 0.0);
+        } else {
+            const double d1 = (log(s / k) + rn * t) / sd + 0.5 * sd;
+            bs = s * 0.5 * erfc(-d1 / sqrt(2.0)) - kd * 0.5 * erfc(-(d1 - sd) / sqrt(2.0));
+        }
+        sum += w * bs;
+        w *= lt / (double)(n + 1);
+        /* past the mode the weights fall faster than the geometric series of ratio lt / (n + 2): that bounds what is left */
+        if ((double)n >= lt && w < 1e-18 * (1.0 - lt / (double)(n + 2)))
+            break;
+    }
+    *price = sum;
+    return MC_OK;
+}

@@ -2417,6 +2417,229 @@ __global__ __launch_bounds__(GROUP) void lookback_kernel(const Tail /* first arg
 }
 
 // =========================================================================================
+// Calls under Merton's jump-diffusion on m equally spaced dates: European, arithmetic-average and discretely monitored barrier
+// (the model is stated in mc_mi355x.h).  Not in the reference.  The first walk here that is DISCONTINUOUS: date j draws, besides
+// its normal z_j, a Poisson count N_j, and given N_j the diffusion plus the jumps of the date is ONE normal of deviation s_{N_j}:
+//   C_j = C_{j-1} + N_j (a per-lane integer),   A_j = fma(s_{N_j}, z_j, A_{j-1}),   x_j = fma(C_j, emu, xk_j) + A_j
+// with xk_j = ln S0 + j a from the per-date table (asian_path's: folded in fp64, rounded once, wave-uniform j: scalar loads).
+// The count is an exact integer inversion of one raw Philox word wd against K wave-uniform thresholds T_0 <= ... <= T_{K-1}
+// (scalar loads again, the compare's scalar operand): N = #{k : wd >= T_k}.  The thresholds are nondecreasing, so the hits of a
+// lane are a prefix and the loop over k ends, for the whole wave, at the first k no lane reaches: a date on which no lane jumps
+// costs ONE compare and a branch, and everything a jump needs sits behind that branch -- per trip of k one compare, one select
+// s = hit ? s_{k+1} : s (a select chain: s_n is the host's fp64-folded value bit for bit, no root and no LDS gather on the
+// device), one add C += hit; then one int-to-float conversion of C per jump date.
+//   EUROPEAN: one exponential at maturity.  ASIAN: one per date, asian_path's.  BARRIER: barrier_path's running minimum of
+//   d_j = fma(A_j, dsg, fma(C_j, dmu, dk_j)) in natural-log units (dk_j = sgn (ln B - ln S0 - j a), dsg = -sgn, dmu = -sgn mu_j),
+//   P by a select, S_T = E(fma(A_m, ex, fma(C_m, emu, xT))).
+//   ANTI: the same at -z on the SAME counts: A^- = -A exactly, so the mirrored path costs no state of its own beyond its sum / minimum.
+// Stream: normals domain 10, the Asian layout; counts domain 11, raw Philox blocks of the same unit: fp32 date j (0-based here) =
+// word j % 4 of block j / 4, fp64 date j = words 2 (j % 2), 2 (j % 2) + 1 of block j / 2 as (lo, hi).
+// =========================================================================================
+enum { MERTON_EUROPEAN = 0, MERTON_ASIAN = 1, MERTON_BARRIER = 2 };   // MC_MERTON_*
+template <class Real> struct MertonWord;
+template <> struct MertonWord<float> { using type = uint32_t; };
+template <> struct MertonWord<double> { using type = uint64_t; };
+
+template <class Real>
+struct MertonArgs {
+    const Real *xk;                                // n_dates values: xk_j in exponent units, or dk_j in natural-log units (barrier)
+    const typename MertonWord<Real>::type *thr;    // n_thr thresholds
+    const Real *sn;                                // n_thr + 1 values: s_0 ... s_K in the units of xk
+    int n_dates, n_thr;
+    typename MertonWord<Real>::type thr0;          // T_0 and s_0 once more, as kernel arguments: every date reads them
+    Real s0;
+    Real emu;         // mu_j in exponent units (natural log in f64, log2 in f32)
+    Real dmu, dsg;    // barrier: -sgn mu_j and -sgn
+    Real xT, ex;      // barrier: ln S_T = xT + emu C_m + ex A_m in exponent units
+    Real strike;
+    Real inv_m;       // 1 / n_dates
+    Real c0, c1;      // barrier: value = (c0 + c1 P) payoff
+};
+
+// One date's count: s enters as s_0 and leaves as s_N, C grows by N, Cf follows C.  Every branch is wave-uniform.
+template <class Real>
+__device__ __forceinline__ void merton_count(const MertonArgs<Real> &o, typename MertonWord<Real>::type wd, Real &s, int &C, Real &Cf)
+{
+    if (o.n_thr <= 0)
+        return;
+    // the table is written before the launch and only read here: through the constant address space its loads are scalar loads
+    // whatever hipcc can prove about the stores around them (inside this loop nest it gives up and emits masked vector loads)
+    const auto *sn = (const __attribute__((address_space(4))) Real *)o.sn;
+    const auto *thr = (const __attribute__((address_space(4))) typename MertonWord<Real>::type *)o.thr;
+    bool hit = wd >= o.thr0;
+    if (__builtin_amdgcn_ballot_w64(hit) == 0)
+        return;
+    int k = 0;
+#pragma unroll 1
+    do {
+        ++k;
+        const Real sk = sn[k];   // taken whether or not a lane selects it: a scalar load and the select's scalar operand
+        s = hit ? sk : s;
+        C += hit ? 1 : 0;
+        if (k >= o.n_thr)
+            break;
+        hit = wd >= thr[k];
+    } while (__builtin_amdgcn_ballot_w64(hit) != 0);
+    Cf = (Real)C;
+}
+
+template <int PAYOFF, class Real>
+__device__ __forceinline__ Real merton_value(Real A, Real Cf, Real sum, Real mn, const MertonArgs<Real> &o)
+{
+    if (PAYOFF == MERTON_ASIAN) {
+        const Real a = fma_r(sum, o.inv_m, -o.strike);
+        return a > 0 ? a : 0;
+    }
+    if (PAYOFF == MERTON_BARRIER) {
+        const Real P = mn > 0 ? (Real)1 : (Real)0;   // the select
+        const Real pay = exp_model(fma_r(A, o.ex, fma_r(Cf, o.emu, o.xT))) - o.strike;
+        return fma_r(o.c1, P, o.c0) * (pay > 0 ? pay : 0);
+    }
+    const Real pay = exp_model(fma_r(Cf, o.emu, o.xk[o.n_dates - 1]) + A) - o.strike;
+    return pay > 0 ? pay : 0;
+}
+
+// fp32: four dates per trip, one block of normals and one raw block of count words.
+template <bool ANTI, int PAYOFF, class Gen>
+__device__ __forceinline__ float merton_path(Gen &gen, const MertonArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "four dates per block of normals and per block of words");
+    const int n = o.n_dates;
+    float A = 0, Cf = 0, sum = 0, sum_m = 0, mn = __builtin_inff(), mn_m = __builtin_inff();
+    int C = 0;
+    float z[NPB];
+    auto date = [&](int j, float zj, uint32_t wd) {
+        float s = o.s0;
+        merton_count(o, wd, s, C, Cf);
+        A = __builtin_fmaf(s, zj, A);
+        if (PAYOFF == MERTON_ASIAN) {
+            const float base = __builtin_fmaf(Cf, o.emu, o.xk[j]);
+            sum += __builtin_amdgcn_exp2f(base + A);
+            if (ANTI)
+                sum_m += __builtin_amdgcn_exp2f(base - A);
+        }
+        if (PAYOFF == MERTON_BARRIER) {
+            const float base = __builtin_fmaf(Cf, o.dmu, o.xk[j]);
+            mn = __builtin_fminf(mn, __builtin_fmaf(A, o.dsg, base));
+            if (ANTI)
+                mn_m = __builtin_fminf(mn_m, __builtin_fmaf(-A, o.dsg, base));
+        }
+    };
+    int j0 = 0;
+    for (; j0 + NPB <= n; j0 += NPB) {
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 10u /*MC_DOMAIN_MERTON*/, z);
+        const u32x4 r = gen.words(w, c0, (uint32_t)(j0 / NPB), 11u /*MC_DOMAIN_MERTON_JUMPS*/);
+        date(j0, z[0], r.x);
+        date(j0 + 1, z[1], r.y);
+        date(j0 + 2, z[2], r.z);
+        date(j0 + 3, z[3], r.w);
+    }
+    if (j0 < n) {   // wave-uniform: one to three dates left
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 10u /*MC_DOMAIN_MERTON*/, z);
+        const u32x4 r = gen.words(w, c0, (uint32_t)(j0 / NPB), 11u /*MC_DOMAIN_MERTON_JUMPS*/);
+        date(j0, z[0], r.x);
+        if (j0 + 1 < n)
+            date(j0 + 1, z[1], r.y);
+        if (j0 + 2 < n)
+            date(j0 + 2, z[2], r.z);
+    }
+    float val = merton_value<PAYOFF>(A, Cf, sum, mn, o);
+    if (ANTI)
+        val = 0.5f * (val + merton_value<PAYOFF>(-A, Cf, sum_m, mn_m, o));
+    return val;
+}
+
+// fp64: asian_path<double>'s loop (Box-Muller pairs through the generator's pair cursor, four pairs per trip, then one); a pair of
+// dates takes its two 64-bit count words from one raw Philox block.  emu (dmu) sits in a vector register for the whole path, so
+// the date's fma reads xk_j from its SGPR pair; the running minimum is min_f64.
+template <bool ANTI, int PAYOFF, class Gen>
+__device__ __forceinline__ double merton_path(Gen &gen, const MertonArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const int n = o.n_dates;
+    double A = 0, Cf = 0, sum = 0, sum_m = 0, mn = __builtin_inf(), mn_m = __builtin_inf();
+    int C = 0;
+    [[maybe_unused]] const double mu_v = to_vgpr(PAYOFF == MERTON_BARRIER ? o.dmu : o.emu);
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto date = [&](int j, double zj, uint32_t lo, uint32_t hi) {
+        double s = o.s0;
+        merton_count(o, ((uint64_t)hi << 32) | lo, s, C, Cf);
+        A = __builtin_fma(s, zj, A);
+        if (PAYOFF == MERTON_ASIAN) {
+            const double base = fma_scalar_addend(Cf, mu_v, o.xk[j]);
+            sum += exp_f64(base + A);
+            if (ANTI)
+                sum_m += exp_f64(base - A);
+        }
+        if (PAYOFF == MERTON_BARRIER) {
+            const double base = fma_scalar_addend(Cf, mu_v, o.xk[j]);
+            mn = min_f64(mn, __builtin_fma(A, o.dsg, base));
+            if (ANTI)
+                mn_m = min_f64(mn_m, __builtin_fma(-A, o.dsg, base));
+        }
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 8 <= n; j += 8) {
+            uint32_t blk = (uint32_t)(j >> 3);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // a pair's generator calls start after the walk (and the sums) of the pair before it, and its count words after its
+                // normals: barrier_path<double>'s tie.  Left free, hipcc overlaps the eight exponentials of a trip
+                if (k)
+                    asm("" : "+v"(A), "+v"(sum), "+v"(sum_m), "+s"(blk));
+                double z0, z1;
+                gen.pair(w, c0, 10u /*MC_DOMAIN_MERTON*/, (blk << 2) | k, carry, z0, z1);
+                uint32_t ub = (blk << 2) | k;
+                asm("" : "+v"(z1), "+s"(ub));
+                const u32x4 r = gen.words(w, c0, ub, 11u /*MC_DOMAIN_MERTON_JUMPS*/);
+                date(j + 2 * (int)k, z0, r.x, r.y);
+                if (PAYOFF == MERTON_ASIAN)   // the second date's exponentials after the first's
+                    asm("" : "+v"(A), "+v"(sum), "+v"(sum_m));
+                date(j + 2 * (int)k + 1, z1, r.z, r.w);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; j += 2) {
+        double z0, z1;
+        gen.pair(w, c0, 10u /*MC_DOMAIN_MERTON*/, (uint32_t)(j >> 1), carry, z0, z1);
+        const u32x4 r = gen.words(w, c0, (uint32_t)(j >> 1), 11u /*MC_DOMAIN_MERTON_JUMPS*/);
+        date(j, z0, r.x, r.y);
+        if (j + 1 < n)   // wave-uniform
+            date(j + 1, z1, r.z, r.w);
+    }
+    gen.pairs_done((uint32_t)((n + 1) >> 1));
+    double val = merton_value<PAYOFF>(A, Cf, sum, mn, o);
+    if (ANTI)
+        val = 0.5 * (val + merton_value<PAYOFF>(-A, Cf, sum_m, mn_m, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths: asian_kernel's frame
+template <class Real, bool ANTI, int PAYOFF, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void merton_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const MertonArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = merton_path<ANTI, PAYOFF>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // European call under the Heston stochastic-volatility model, full-truncation Euler in log space on m equal steps (the model
 // is stated in mc_mi355x.h).  Not in the reference.  The first walk here whose step is non-linear in its state: besides the
 // normals a lane carries the variance V and two running sums, because

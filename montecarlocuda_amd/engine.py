@@ -153,6 +153,19 @@ def _as_heston_path(X, o, model=None, n_dates=None, steps_per_date=None, payoff=
     return _lib.HESTON_PATH[X](h, int(steps_per_date), payoff, kind, 0.0 if barrier is None else float(barrier))
 
 
+def _as_merton(X, o, jumps=None, n_dates=None, payoff=None, barrier=None, kind=None) -> C.Structure:
+    """mc_merton_*: an option (OptionData or dict) with the jumps {lambda, mu_j, delta}, the contract's n_dates and the payoff
+    ("european", "asian" or "barrier", then with the barrier and its kind), or a dict that carries the jumps' three fields,
+    "n_dates", optionally "payoff" and for the barrier "barrier" and optionally "kind" itself."""
+    if jumps is None:
+        jumps, n_dates, payoff = o, o["n_dates"], o.get("payoff", "european")
+        barrier, kind = o.get("barrier"), o.get("kind", "up-and-out")
+    payoff = _lib.MERTON_PAYOFFS[payoff] if isinstance(payoff, str) else int(payoff)
+    kind = 0 if kind is None else _lib.BARRIER_TYPES[kind] if isinstance(kind, str) else int(kind)
+    return _lib.MERTON[X](_as_option(X, o), float(jumps["lambda"]), float(jumps["mu_j"]), float(jumps["delta"]), int(n_dates), payoff, kind,
+                          0.0 if barrier is None else float(barrier))
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -431,6 +444,21 @@ class Engine:
         return self._run("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
                          first_path, n_paths)
 
+    def merton(self, opt, jumps, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """European call under Merton's jump-diffusion, walked over n_dates equally spaced dates (mc_merton_run_*; exact in law
+        at any n_dates, merton_closed_form).  jumps: a dict with lambda, mu_j, delta.  Honours set_antithetic."""
+        return self._run("merton", precision, _as_merton(precision, opt, jumps, n_dates, "european"), seed, first_path, n_paths)
+
+    def merton_asian(self, opt, jumps, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """Arithmetic-average call over n_dates equally spaced dates under Merton's jump-diffusion (mc_merton_run_*)."""
+        return self._run("merton", precision, _as_merton(precision, opt, jumps, n_dates, "asian"), seed, first_path, n_paths)
+
+    def merton_barrier(self, opt, jumps, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64",
+                       kind="up-and-out") -> Estimate:
+        """Single-barrier call under Merton's jump-diffusion, the barrier monitored on the n_dates dates only (mc_merton_run_*).
+        kind as for barrier(); there is no continuous monitoring."""
+        return self._run("merton", precision, _as_merton(precision, opt, jumps, n_dates, "barrier", barrier, kind), seed, first_path, n_paths)
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
@@ -452,6 +480,8 @@ class Engine:
             return _as_heston(precision, inputs), None
         if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
             return _as_heston_path(precision, inputs), None
+        if prod == "merton":   # inputs: the option's fields plus "lambda", "mu_j", "delta", "n_dates" and optionally "payoff", "barrier", "kind"
+            return _as_merton(precision, inputs), None
         if prod == "lookback":   # inputs: the option's fields plus "n_dates" and optionally "kind", "monitoring"
             return _as_lookback(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
@@ -485,6 +515,15 @@ class Engine:
     def lookback_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
                        monitoring="discrete"):
         return self._paths("lookback", precision, _as_lookback(precision, opt, n_dates, kind, monitoring), seed, first_path, n_paths)
+
+    def merton_paths(self, opt, jumps, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("merton", precision, _as_merton(precision, opt, jumps, n_dates, "european"), seed, first_path, n_paths)
+
+    def merton_asian_paths(self, opt, jumps, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("merton", precision, _as_merton(precision, opt, jumps, n_dates, "asian"), seed, first_path, n_paths)
+
+    def merton_barrier_paths(self, opt, jumps, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out"):
+        return self._paths("merton", precision, _as_merton(precision, opt, jumps, n_dates, "barrier", barrier, kind), seed, first_path, n_paths)
 
     def heston_paths(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
@@ -620,6 +659,23 @@ def lookback_closed_form(opt, kind="floating-call", precision="f64"):
     p = C.c_double()
     check(getattr(lib(), f"mc_lookback_closed_form_{precision}")(C.byref(_as_lookback(precision, opt, 1, kind, "continuous")), C.byref(p)))
     return p.value
+
+
+def merton_closed_form(opt, jumps, precision="f64"):
+    """Discounted exact price of the European call under Merton's jump-diffusion (Merton's series of Black-Scholes prices; fp64)."""
+    p = C.c_double()
+    check(getattr(lib(), f"mc_merton_closed_form_{precision}")(C.byref(_as_merton(precision, opt, jumps, 1, "european")), C.byref(p)))
+    return p.value
+
+
+def merton_thresholds(opt, jumps, n_dates, precision="f64"):
+    """The integer thresholds T_0 <= ... <= T_{K-1} of the Poisson(lambda t / n_dates) count drawn from a 32-bit (f32) or 64-bit
+    (f64) word: N = #{k : word >= T_k} (mc_merton_thresholds_*).  A uint64 array of length K."""
+    out = np.zeros(_lib.MAX_MERTON_JUMPS, dtype=np.uint64)
+    n = C.c_int()
+    check(getattr(lib(), f"mc_merton_thresholds_{precision}")(C.byref(_as_merton(precision, opt, jumps, n_dates, "european")),
+                                                               out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+    return out[:n.value].copy()
 
 
 def heston_closed_form(opt, model, precision="f64"):
