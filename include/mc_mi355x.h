@@ -75,6 +75,8 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_LOOKBACK_BRIDGE 9u /* the lookback call's uniforms: raw Philox blocks, see mc_lookback_run_* */
 #define MC_DOMAIN_MERTON 10u
 #define MC_DOMAIN_MERTON_JUMPS 11u /* the jump-diffusion's Poisson counts: raw Philox blocks, see mc_merton_run_* */
+#define MC_DOMAIN_AMERICAN 12u /* the pricing pass of the Bermudan options, see mc_american_run_* */
+#define MC_DOMAIN_AMERICAN_FIT 13u /* the fit of their exercise rule, see mc_american_fit_*: never the paths the rule is priced on */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -156,6 +158,21 @@ typedef struct { mc_heston_f64 heston; int steps_per_date, payoff, barrier_type;
 enum { MC_MERTON_EUROPEAN = 0, MC_MERTON_ASIAN = 1, MC_MERTON_BARRIER = 2 };
 typedef struct { mc_option_f32 option; float lambda, mu_j, delta; int n_dates, payoff, barrier_type; float barrier; } mc_merton_f32;
 typedef struct { mc_option_f64 option; double lambda, mu_j, delta; int n_dates, payoff, barrier_type; double barrier; } mc_merton_f64;
+
+/* Bermudan put or call on n_dates equally spaced exercise dates t_j = j t / n_dates, j = 1 ... n_dates (t_0 is no exercise date),
+ * priced under a GIVEN exercise rule: a table beta of n_dates x 4 doubles, row j - 1 the cubic in the payoff that estimates the
+ * value of continuing at date j (see mc_american_run_*).  Not in the reference.  type is MC_AMERICAN_PUT or MC_AMERICAN_CALL;
+ * degree (1..3) is the degree of the polynomial a Longstaff-Schwartz fit of the rule regresses on (mc_american_solve); the
+ * pricing calls check its range and otherwise ignore it.  The per-date constants travel as a table of SIX values per date
+ * (xk_j, g_j, beta_j0..3), folded in fp64 and rounded once, read through scalar loads: the cap is the largest power of two
+ * that keeps that table (12 KB in fp32, 24 KB in fp64) within the Asian call's (16 KB, 32 KB), the size of the scalar data
+ * cache; 4096 dates would need 96 KB and 192 KB. */
+#define MC_MAX_AMERICAN_DATES 512
+#define MC_AMERICAN_MIN_ITM 32   /* mc_american_solve: a date with fewer paths in the money gets the never-exercise row */
+#define MC_AMERICAN_SUMS 11      /* mc_american_solve: sum p^k, k = 0 ... 6, then sum p^k V, k = 0 ... 3 */
+enum { MC_AMERICAN_PUT = 0, MC_AMERICAN_CALL = 1 };
+typedef struct { mc_option_f32 option; int n_dates, type, degree; } mc_american_f32;
+typedef struct { mc_option_f64 option; int n_dates, type, degree; } mc_american_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -597,6 +614,66 @@ int mc_merton_closed_form_f32(const mc_merton_f32 *opt, double *price);
 int mc_merton_closed_form_f64(const mc_merton_f64 *opt, double *price);
 int mc_merton_thresholds_f32(const mc_merton_f32 *opt, uint64_t *out, int *count);
 int mc_merton_thresholds_f64(const mc_merton_f64 *opt, uint64_t *out, int *count);
+
+/* ---- Bermudan put and call under a given exercise rule (the pricing pass of Longstaff-Schwartz) ---------------------------
+ * m = n_dates, dt = t/m, a = (r - v^2/2) dt, bx = v sqrt(dt), W_j = z_1 + ... + z_j, and in units of the strike
+ *     x_j = ln(s/k) + j a + bx W_j,   e_j = exp(x_j),   q = -1 (put) or +1 (call),   p_j = max(q (e_j - 1), 0),
+ *     g_j = exp(r (t - t_j))          (a payoff taken at t_j, compounded to t).
+ * The rule is the m x 4 table beta: C_j(p) = ((beta_j3 p + beta_j2) p + beta_j1) p + beta_j0 estimates, in the same units, the
+ * value of NOT exercising at date j.  At date j < m the holder exercises iff p_j > 0 and p_j g_j > C_j(p_j); at date m iff
+ * p_m > 0 (row m of beta is ignored, whatever it holds).  A row {+inf, 0, 0, 0} means "never on this date": in the Horner form
+ * above it stays free of NaN for every finite p.  Per path, walking forward: the value is p_tau g_tau at the FIRST date tau that
+ * exercises, else 0 -- in units of k, compounded to t.  The calls scale the sums by k and k^2 and the closing's exp(-r t) then
+ * gives the price, as for every other product; mc_american_paths_* returns the per-path values unscaled (units of k).
+ * mc_context_set_antithetic: the mean of the value at z and at -z, each direction with its own exercise date.
+ * Any rule gives a LOWER bound of the Bermudan price (it is one admissible exercise policy) as long as beta was not fitted on the
+ * paths it is priced on: path p is unit p of MC_DOMAIN_AMERICAN, a domain no fit draws from; date j (1-based) draws entry
+ * (j - 1) % npb of block (j - 1) / npb: the Asian layout under its own domain word.  MC_STREAM_VERSION stays 2.
+ * MC_ERR_INVALID before anything is enqueued: n_dates outside [1, MC_MAX_AMERICAN_DATES]; type or degree out of range;
+ * s <= 0, k <= 0, t <= 0, v < 0 or a non-finite input; in rows 1 ... m - 1 a beta entry that is NaN, or -inf, or infinite outside
+ * column 0 (after rounding to the kernel's precision); the control variate switched on (there is none); a generator other than
+ * Philox; drift and volatility that can put |ln(s/k)| + m (|a| + bx z_max) outside the device exponential's range.
+ * MC_ERR_UNSUPPORTED: MC_NORMALS_F32 on the _f64 calls, a context set up for external normals or the launch geometry.  The
+ * context stays usable.  Path ranges, the finish, call statistics, timing, arming and ordering as for the other products;
+ * several GPUs through mc_american_launch_* + mc_shard_range + mc_closing.  n_paths <= 2^26 for mc_american_paths_*.
+ *
+ * mc_american_fit_*: the rule by Longstaff-Schwartz on n_paths <= 2^24 paths of their own.  Backward from maturity, V = p_m; for
+ * j = m - 1 ... 1: beta_j = the regression of V on {1, p_j, ..., p_j^degree} over the paths with p_j > 0 (mc_american_solve on sums
+ * accumulated in fp64 in both precisions), then V = exercise_j ? p_j g_j : V with the decision above.  The path is never stored:
+ * W_m = sqrt(m) z_m and W_j = j/(j+1) W_{j+1} + sqrt(j/(j+1)) z_j, the Brownian bridge from 0, is a Brownian motion at 1 ... m
+ * walked backward, exact in law; the per-path state (W, V) lives in device memory owned by the context.  One kernel launch per date
+ * and a one-lane solve between two of them, 2 m + 1 launches on the context's stream without a host synchronisation in between.
+ * beta receives n_dates x 4 doubles (row m zero; in fp32 the kernels apply each row rounded once to float); *in_sample the
+ * estimate from the fit's own paths -- biased HIGH, the rule having seen them -- closed like every other result (kernel_ms spans
+ * the whole fit).  Path p is unit p of MC_DOMAIN_AMERICAN_FIT, the Asian layout: whatever seed and range, no path is shared with
+ * the pricing pass.  The estimator is always the plain one (mc_context_set_antithetic concerns the pricing pass).  Refusals as
+ * for mc_american_run_*, plus n_paths > 2^24; synchronous, on the context's stream.  The fit always brackets its launches with HIP
+ * events and reports kernel_ms, also after mc_context_set_timing(ctx, 0) (as the Greeks calls do: it waits on the stream anyway).
+ *
+ * mc_american_solve (plain C, no GPU): ONE date's regression of a Longstaff-Schwartz fit.  sums holds MC_AMERICAN_SUMS doubles
+ * taken over the paths in the money at that date: sums[k] = sum p^k, k = 0 ... 6 (sums[0] their number), sums[7 + k] = sum p^k V,
+ * k = 0 ... 3, V the path's value from the later dates (units of k, compounded to t).  Only k <= 2 degree and k <= degree are
+ * read.  The normal equations of V on {1, p, ..., p^degree} are solved in fp64 by Cholesky on the Jacobi-scaled matrix (row and
+ * column i divided by the root of the i-th diagonal entry): beta[0 ... degree] the coefficients, the rest 0.  Fewer than
+ * MC_AMERICAN_MIN_ITM paths in the money, or a pivot that is not positive, give the never-exercise row {+inf, 0, 0, 0}.
+ * Returns MC_OK in both cases; MC_ERR_INVALID for a NULL argument or degree outside 1..3.
+ *
+ * mc_american_lattice_*: the discounted Cox-Ross-Rubinstein binomial price of the SAME contract (exercise on the m dates only)
+ * on m steps_per_date steps, u = exp(v sqrt(h)), d = 1/u, h = t / (m steps_per_date), risk-neutral probability
+ * (exp(r h) - d)/(u - d); fp64, plain C, no GPU.  Needs v > 0, a probability inside (0, 1) and at most 2^15 steps. */
+int mc_american_run_f32(mc_context *ctx, const mc_american_f32 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_american_run_f64(mc_context *ctx, const mc_american_f64 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_american_launch_f32(mc_context *ctx, const mc_american_f32 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_american_launch_f64(mc_context *ctx, const mc_american_f64 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_american_paths_f32(mc_context *ctx, const mc_american_f32 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_american_paths_f64(mc_context *ctx, const mc_american_f64 *opt, const double *beta, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_american_fit_f32(mc_context *ctx, const mc_american_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *beta, mc_result *in_sample);
+int mc_american_fit_f64(mc_context *ctx, const mc_american_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *beta, mc_result *in_sample);
+int mc_american_solve(const double *sums, int degree, double beta[4]);
+int mc_american_lattice_f32(const mc_american_f32 *opt, int steps_per_date, double *price);
+int mc_american_lattice_f64(const mc_american_f64 *opt, int steps_per_date, double *price);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

@@ -74,6 +74,17 @@ int mc_cva_from_normals_f32(mc_context *ctx, const mc_cva_f32 *cva, const float 
 int mc_cva_from_normals_f64(mc_context *ctx, const mc_cva_f64 *cva, const double *h_normals, uint64_t n_paths,
                             int flags, double *h_values, mc_result *out);
 
+/* ---- ONE date launch of the Longstaff-Schwartz fit (mc_american_fit_*, mc_mi355x.h) on caller-supplied state ------------------
+ * Walks n_paths paths from date j + 1 to date j (j = n_dates ... 0): applies date j + 1's decision with the rule row beta_next
+ * (4 doubles; read when j + 1 < n_dates) to the HOST arrays (h_W, h_V) = (W_{j+1}, V) (read when j < n_dates), takes the bridge
+ * step with the normal of date j of unit first_path + i in MC_DOMAIN_AMERICAN_FIT, and returns (W_j, V) in the same arrays (j > 0)
+ * and the launch's twelve raw sums in `sums`: for 0 < j < n_dates sum p_j^k, k = 0 ... 6, then sum p_j^k V, k = 0 ... 3, over the
+ * paths with p_j > 0 (slot 11 is 0); for j = 0 sum V and sum V^2 (the rest 0); for j = n_dates all 0. */
+int mc_american_fit_date_f32(mc_context *ctx, const mc_american_f32 *opt, int j, const double *beta_next, uint64_t seed, uint64_t first_path,
+                             uint64_t n_paths, float *h_W, float *h_V, double *sums);
+int mc_american_fit_date_f64(mc_context *ctx, const mc_american_f64 *opt, int j, const double *beta_next, uint64_t seed, uint64_t first_path,
+                             uint64_t n_paths, double *h_W, double *h_V, double *sums);
+
 /* ---- launch-geometry mode (mc_*_run_grid_*, mc_mi355x.h): the two forms side by side ------------------------------------
  * MC_GRID_FORM_AUTO (default): the fused kernels where they exist, the staged form otherwise.  _STAGED: always round 3's
  * staged form (normals through HBM, priced by the engine's kernels) -- the checker.  _FUSED: the fused kernels or

@@ -25,6 +25,11 @@ DOMAIN_MERTON, DOMAIN_MERTON_JUMPS = 10, 11   # normals; the Poisson counts (raw
 MAX_MERTON_DATES = 4096   # MC_MAX_MERTON_DATES
 MAX_MERTON_JUMPS = 40   # MC_MAX_MERTON_JUMPS
 MERTON_PAYOFFS = {"european": 0, "asian": 1, "barrier": 2}   # MC_MERTON_EUROPEAN, MC_MERTON_ASIAN, MC_MERTON_BARRIER
+DOMAIN_AMERICAN, DOMAIN_AMERICAN_FIT = 12, 13   # the pricing pass of the Bermudan options; the fit of their rule
+MAX_AMERICAN_DATES = 512   # MC_MAX_AMERICAN_DATES
+AMERICAN_MIN_ITM = 32   # MC_AMERICAN_MIN_ITM
+AMERICAN_SUMS = 11   # MC_AMERICAN_SUMS
+AMERICAN_TYPES = {"put": 0, "call": 1}   # MC_AMERICAN_PUT, MC_AMERICAN_CALL
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
 LOOKBACK_TYPES = {"floating-call": 0, "floating-put": 1, "fixed-call": 2, "fixed-put": 3}   # MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
@@ -102,6 +107,14 @@ class MertonF64(C.Structure):   # mc_merton_f64
                 ("barrier_type", C.c_int), ("barrier", C.c_double)]
 
 
+class AmericanF32(C.Structure):   # mc_american_f32
+    _fields_ = [("option", OptionF32), ("n_dates", C.c_int), ("type", C.c_int), ("degree", C.c_int)]
+
+
+class AmericanF64(C.Structure):   # mc_american_f64
+    _fields_ = [("option", OptionF64), ("n_dates", C.c_int), ("type", C.c_int), ("degree", C.c_int)]
+
+
 class HestonF32(C.Structure):   # mc_heston_f32
     _fields_ = [("option", OptionF32), ("v0", C.c_float), ("kappa", C.c_float), ("theta", C.c_float), ("xi", C.c_float), ("rho", C.c_float),
                 ("n_steps", C.c_int)]
@@ -160,6 +173,7 @@ BARRIER = {"f32": BarrierF32, "f64": BarrierF64}
 LOOKBACK = {"f32": LookbackF32, "f64": LookbackF64}
 HESTON = {"f32": HestonF32, "f64": HestonF64}
 MERTON = {"f32": MertonF32, "f64": MertonF64}
+AMERICAN = {"f32": AmericanF32, "f64": AmericanF64}
 HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
 
@@ -171,6 +185,7 @@ EXPORTS = ["mc_last_error", "mc_device_count", "mc_device_pci_bus_id", "mc_conte
            "mc_context_order", "mc_context_idle", "mc_context_arm_direct", "mc_context_publish", "mc_context_set_generator",
            "mc_context_set_normals", "mc_context_set_cva_date_lanes", "mc_basket_control_mean_f32", "mc_basket_control_mean_f64", "mc_closing", "mc_shard_range",
            "mc_chol_f32", "mc_chol_f64", "mc_factor_from_cov_f32", "mc_factor_from_cov_f64"]
+EXPORTS.append("mc_american_solve")
 TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_set_grid_form"]
 for _x in ("f32", "f64"):
     for _p in ("vanilla", "basket", "cva"):
@@ -184,6 +199,8 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
     EXPORTS += [f"mc_merton_run_{_x}", f"mc_merton_launch_{_x}", f"mc_merton_paths_{_x}", f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}"]
+    EXPORTS += [f"mc_american_run_{_x}", f"mc_american_launch_{_x}", f"mc_american_paths_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
+    TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
     EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
     EXPORTS += [f"mc_heston_path_run_{_x}", f"mc_heston_path_launch_{_x}", f"mc_heston_path_paths_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
@@ -225,6 +242,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.mc_context_set_grid_form.argtypes = [ctx, C.c_int]
     L.mc_words.argtypes = [ctx, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.mc_xorwow_words.argtypes = [ctx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.mc_american_solve.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     for X in ("f32", "f64"):
         getattr(L, f"mc_basket_control_mean_{X}").argtypes = [C.POINTER(BASKET[X]), C.POINTER(C.c_double)]
     L.mc_context_profile.argtypes = [ctx, C.c_int]
@@ -276,6 +294,13 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_merton_paths_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, RP]
         getattr(L, f"mc_merton_closed_form_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_double)]
         getattr(L, f"mc_merton_thresholds_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        DP = C.POINTER(C.c_double)
+        getattr(L, f"mc_american_launch_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_american_run_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_american_paths_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, RP]
+        getattr(L, f"mc_american_lattice_{X}").argtypes = [C.POINTER(AMERICAN[X]), C.c_int, DP]
+        getattr(L, f"mc_american_fit_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), u64, u64, u64, DP, C.POINTER(Result)]
+        getattr(L, f"mc_american_fit_date_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), C.c_int, DP, u64, u64, u64, RP, RP, DP]
         getattr(L, f"mc_heston_launch_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -84,7 +85,9 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a jump-diffusion call's dates, thresholds and s_n, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
+    void *fit_state = nullptr;    // a Longstaff-Schwartz fit's per-path state (W, V), its device table and the fp64 copy of beta: grown on demand
+    size_t fit_state_bytes = 0;
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // generator: Philox (counter-based, stateless) or XORWOW (one sequence per lane: mc_rng.hpp GenXorwow)
@@ -390,6 +393,7 @@ extern "C" void mc_context_destroy(mc_context *c)
     if (c->last_use) (void)hipEventDestroy(c->last_use);
     (void)hipFree(c->d_triple);
     (void)hipFree(c->g_pairs);
+    (void)hipFree(c->fit_state);
     (void)hipFree(c->g_triples);
     (void)hipHostFree(c->h_triple);
     (void)hipHostFree(c->h_direct);
@@ -2498,6 +2502,252 @@ static int merton_enqueue(mc_context *c, const typename MertonIn<Real>::type *v,
         });
 }
 
+// ---------------------------------------------------------------------------------------
+// Bermudan put / call under a given exercise rule (the pricing pass of Longstaff-Schwartz): american_kernel, one lane per path
+// ---------------------------------------------------------------------------------------
+template <class Real> struct AmericanIn;
+template <> struct AmericanIn<float> { using type = mc_american_f32; };
+template <> struct AmericanIn<double> { using type = mc_american_f64; };
+static int american_check(const mc_american_f32 &o) { return mc_american_check_f32(&o); }
+static int american_check(const mc_american_f64 &o) { return mc_american_check_f64(&o); }
+
+// The checks of the contract and of the rule, and the table's rows {xk_j, g_j, beta_j0 .. beta_j3}, j = 1 ... n_dates, each value
+// folded in fp64 and rounded once; the last row's rule is {-inf, 0, 0, 0} (exercise iff in the money: american_kernel).  Host only:
+// nothing is enqueued and no table is touched.
+template <class Real>
+static int american_rows(const typename AmericanIn<Real>::type *v, const double *beta, std::vector<Real> &tab, AmericanArgs<Real> &args)
+{
+    if (int rc = american_check(*v)) return rc;
+    if (!beta)
+        return fail(MC_ERR_INVALID, "american: NULL exercise rule");
+    const auto &o = v->option;
+    const double sc = exp_scale<Real>();
+    const int nd = v->n_dates;
+    const double m = (double)nd, dt = (double)o.t / m;
+    const double a = ((double)o.r - 0.5 * (double)o.v * (double)o.v) * dt, bx = (double)o.v * std::sqrt(dt), x0 = std::log((double)o.s / (double)o.k);
+    // as for the Asian call: only the hard limit of the device's exp is enforced
+    if (!(std::fabs(x0) + m * (std::fabs(a) + bx * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+        return fail(MC_ERR_INVALID, "american: drift and volatility put the simulated spot outside the range of a double");
+    tab.resize((size_t)nd * AMERICAN_ROW);
+    for (int j = 1; j <= nd; ++j) {
+        Real *row = &tab[(size_t)(j - 1) * AMERICAN_ROW];
+        row[0] = (Real)((x0 + (double)j * a) * sc);
+        row[1] = (Real)std::exp((double)o.r * ((double)o.t - (double)j * dt));
+        if (j == nd) {
+            row[2] = -std::numeric_limits<Real>::infinity(), row[3] = row[4] = row[5] = 0;
+            break;
+        }
+        for (int q = 0; q < 4; ++q) {
+            const Real b = (Real)beta[(size_t)(j - 1) * 4 + (size_t)q];
+            if (std::isnan((double)b) || (std::isinf((double)b) && (q > 0 || b < 0)))
+                return fail(MC_ERR_INVALID, "american: beta[%d][%d]=%g: a rule's entries are finite, or +inf in column 0", j - 1, q,
+                            beta[(size_t)(j - 1) * 4 + (size_t)q]);
+            row[2 + q] = b;
+        }
+    }
+    args.n_dates = nd;
+    args.bx = (Real)(bx * sc);
+    args.q = v->type == MC_AMERICAN_PUT ? (Real)-1 : (Real)1;
+    return MC_OK;
+}
+
+template <class Real>
+static int american_enqueue(mc_context *c, const typename AmericanIn<Real>::type *v, const double *beta, uint64_t seed, uint64_t first,
+                            uint64_t n, double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "american: no external-normals or launch-geometry form");
+    if (c->rng != MC_RNG_PHILOX)
+        return fail(MC_ERR_INVALID, "american: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "american: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_INVALID, "american: no control variate");
+    static thread_local std::vector<Real> tab;
+    AmericanArgs<Real> args;
+    if (int rc = american_rows<Real>(v, beta, tab, args)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    if (int rc = c->table.upload(c, st, table_key(tab, 'E'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    args.rows = (const Real *)c->table.d;
+    const double k = (double)v->option.k;   // the per-path values are in units of the strike
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, k, k * k, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) launch_sim(prof, american_kernel<Real, true>, g, st, t, args, w, dst);
+            else               launch_sim(prof, american_kernel<Real, false>, g, st, t, args, w, dst);
+            return MC_OK;
+        });
+}
+
+// ---- the fit of the rule (american_fit_kernel, american_solve_kernel) ----
+// One buffer per context, grown on demand behind quiesce: W and V (n Reals each), the device table (n_dates rows), beta in fp64
+// (n_dates x 4), every part 256-byte aligned.
+template <class Real> struct FitBuffers { Real *W, *V, *rows; double *beta64; };
+template <class Real>
+static int fit_buffers(mc_context *c, uint64_t n, int n_dates, FitBuffers<Real> &b)
+{
+    const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t state = up((size_t)n * sizeof(Real)), rows = up((size_t)n_dates * AMERICAN_ROW * sizeof(Real)), beta = up((size_t)n_dates * 4 * sizeof(double));
+    const size_t bytes = 2 * state + rows + beta;
+    if (c->fit_state_bytes < bytes) {
+        if (int rc = quiesce(c)) return rc;
+        if (c->fit_state) HIPCHK(hipFree(c->fit_state));
+        c->fit_state = nullptr, c->fit_state_bytes = 0;
+        if (hipMalloc(&c->fit_state, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MC_ERR_HIP, "american fit: cannot allocate %zu bytes of device memory", bytes);
+        }
+        c->fit_state_bytes = bytes;
+    }
+    char *p = (char *)c->fit_state;
+    b.W = (Real *)p, b.V = (Real *)(p + state), b.rows = (Real *)(p + 2 * state), b.beta64 = (double *)(p + 2 * state + rows);
+    return MC_OK;
+}
+
+// ONE date launch of the fit as one call on six planes: the date's sums arrive in c->g_triples, scaled by (scale1, scale2)
+template <class Real>
+static int fit_date_enqueue(mc_context *c, hipStream_t st, const FitBuffers<Real> &b, const AmericanArgs<Real> &a, int j, uint64_t seed,
+                            const std::vector<Segment> &segs, uint64_t n, double scale1, double scale2)
+{
+    AmericanFitArgs<Real> f;
+    f.rows = b.rows, f.j = j, f.n_dates = a.n_dates, f.bx = a.bx, f.q = a.q;
+    f.cw = j == a.n_dates ? (Real)0 : (Real)((double)j / ((double)j + 1.0));
+    f.cz = j == a.n_dates ? (Real)std::sqrt((double)j) : (Real)std::sqrt((double)j / ((double)j + 1.0));
+    const Planes where = {c->g_pairs, AMERICAN_FIT_PLANES, 2 * c->blocks + 2, 1};
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, scale1, scale2, n, c->g_triples, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            f.W = b.W + done, f.V = b.V + done;
+            launch_sim(prof, american_fit_kernel<Real>, g, st, t, f, context_work(c, seed, s, 0, 0));
+            return MC_OK;
+        },
+        where);
+}
+
+template <class Real>
+static void solve_launch(hipStream_t st, int degree, const double *triples, Real *row_beta, double *beta64)
+{
+    if (degree == 1)      american_solve_kernel<Real, 1><<<1, 64, 0, st>>>(triples, row_beta, beta64);
+    else if (degree == 2) american_solve_kernel<Real, 2><<<1, 64, 0, st>>>(triples, row_beta, beta64);
+    else                  american_solve_kernel<Real, 3><<<1, 64, 0, st>>>(triples, row_beta, beta64);
+}
+
+static constexpr uint64_t MAX_FIT_PATHS = 1ull << 24;
+
+// what every entry point of the fit refuses and prepares: the pricing pass's refusals, the contract's checks, the path count, the
+// buffers, the planes, the segments (a plane holds the pairs of two launches) and the device table with the rule left zero
+template <class Real>
+static int fit_prepare(mc_context *c, const typename AmericanIn<Real>::type *v, uint64_t first, uint64_t n, hipStream_t st, FitBuffers<Real> &b,
+                       AmericanArgs<Real> &args, std::vector<Segment> &segs)
+{
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "american fit: no external-normals or launch-geometry form");
+    if (c->rng != MC_RNG_PHILOX)
+        return fail(MC_ERR_INVALID, "american fit: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "american fit: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_INVALID, "american fit: no control variate");
+    if (n > MAX_FIT_PATHS)
+        return fail(MC_ERR_INVALID, "american fit: at most 2^24 paths (the state of every path lives in device memory)");
+    if (int rc = american_check(*v)) return rc;   // before anything is sized by n_dates
+    static thread_local std::vector<Real> tab;
+    static thread_local std::vector<double> zero;
+    zero.assign((size_t)v->n_dates * 4, 0.0);
+    if (int rc = american_rows<Real>(v, zero.data(), tab, args)) return rc;
+    for (int q = 2; q < AMERICAN_ROW; ++q)   // the last row's rule is never read by the fit; keep the table free of infinities
+        tab[(size_t)(v->n_dates - 1) * AMERICAN_ROW + (size_t)q] = 0;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (segs.size() > 2)
+        return fail(MC_ERR_INVALID, "american fit: path range too large for one call; split it");
+    if (int rc = begin_call(c, st)) return rc;
+    if (int rc = ensure_planes(c, AMERICAN_FIT_PLANES)) return rc;
+    if (int rc = fit_buffers<Real>(c, n, v->n_dates, b)) return rc;
+    HIPCHK(hipMemcpyAsync(b.rows, tab.data(), tab.size() * sizeof(Real), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b.beta64, 0, (size_t)v->n_dates * 4 * sizeof(double), st));
+    args.rows = b.rows;
+    return MC_OK;
+}
+
+// The whole fit: 2 m + 1 launches on the context's stream, no host synchronisation in between; then beta and the in-sample triple come back.
+template <class Real>
+static int american_fit(mc_context *c, const typename AmericanIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n, double *beta,
+                        mc_result *in_sample)
+{
+    const auto wall0 = host_clock::now();
+    hipStream_t st = c->stream;
+    FitBuffers<Real> b;
+    AmericanArgs<Real> args;
+    std::vector<Segment> segs;
+    if (int rc = fit_prepare<Real>(c, v, first, n, st, b, args, segs)) return rc;
+    const int m = v->n_dates;
+    const double k = (double)v->option.k;
+    HIPCHK(hipMemsetAsync(c->g_triples, 0xFF, sizeof(double) * 3 * AMERICAN_FIT_PLANES, st));   // poison: see run_sync
+    HIPCHK(hipEventRecord(c->ev0, st));
+    for (int j = m; j >= 0; --j) {
+        if (int rc = fit_date_enqueue<Real>(c, st, b, args, j, seed, segs, n, j == 0 ? k : 1.0, j == 0 ? k * k : 1.0)) return rc;
+        if (j >= 1 && j < m)
+            solve_launch<Real>(st, v->degree, c->g_triples, b.rows + (size_t)(j - 1) * AMERICAN_ROW + 2, b.beta64 + (size_t)(j - 1) * 4);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, st));
+    double h[3];
+    HIPCHK(hipMemcpyAsync(h, c->g_triples, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(beta, b.beta64, (size_t)m * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (int rc = close_triple(h, n, std::exp(-(double)v->option.r * (double)v->option.t), ms, in_sample)) return rc;
+    in_sample->wall_ms = std::chrono::duration<float, std::milli>(host_clock::now() - wall0).count();
+    return MC_OK;
+}
+
+// Test hook: ONE date launch on host-supplied state and rule (mc_mi355x_test.h)
+template <class Real>
+static int american_fit_date(mc_context *c, const typename AmericanIn<Real>::type *v, int j, const double *beta_next, uint64_t seed, uint64_t first,
+                             uint64_t n, Real *h_W, Real *h_V, double *h_sums)
+{
+    hipStream_t st = c->stream;
+    FitBuffers<Real> b;
+    AmericanArgs<Real> args;
+    std::vector<Segment> segs;
+    if (j < 0 || j > v->n_dates)
+        return fail(MC_ERR_INVALID, "american fit date: j=%d outside [0, n_dates]", j);
+    if (int rc = fit_prepare<Real>(c, v, first, n, st, b, args, segs)) return rc;
+    if (j + 1 < v->n_dates) {   // row j + 1 of the rule, rounded once
+        Real row[4];
+        for (int q = 0; q < 4; ++q)
+            row[q] = (Real)beta_next[q];
+        HIPCHK(hipMemcpyAsync(b.rows + (size_t)j * AMERICAN_ROW + 2, row, sizeof row, hipMemcpyHostToDevice, st));
+    }
+    if (j < v->n_dates) {
+        HIPCHK(hipMemcpyAsync(b.W, h_W, (size_t)n * sizeof(Real), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b.V, h_V, (size_t)n * sizeof(Real), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemsetAsync(c->g_triples, 0xFF, sizeof(double) * 3 * AMERICAN_FIT_PLANES, st));
+    if (int rc = fit_date_enqueue<Real>(c, st, b, args, j, seed, segs, n, 1.0, 1.0)) return rc;
+    double h[3 * AMERICAN_FIT_PLANES];
+    HIPCHK(hipMemcpyAsync(h, c->g_triples, sizeof h, hipMemcpyDeviceToHost, st));
+    if (j > 0) {
+        HIPCHK(hipMemcpyAsync(h_W, b.W, (size_t)n * sizeof(Real), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_V, b.V, (size_t)n * sizeof(Real), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int q = 0; q < AMERICAN_FIT_PLANES; ++q) {
+        if (!(h[3 * q + 2] == (double)n))
+            return fail(MC_ERR_HIP, "american fit date: the launch's final reduction did not complete");
+        h_sums[2 * q] = h[3 * q], h_sums[2 * q + 1] = h[3 * q + 1];
+    }
+    return MC_OK;
+}
+
 template <class Real> struct HestonIn;
 template <> struct HestonIn<float> { using type = mc_heston_f32; };
 template <> struct HestonIn<double> { using type = mc_heston_f64; };
@@ -3545,6 +3795,44 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return merton_enqueue<Real>(c, o, seed, first, n, t, st, d);                                     \
         });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_american_launch_##X(mc_context *c, const mc_american_##X *o, const double *beta, uint64_t seed,\
+                                          uint64_t first, uint64_t n, double *d_triple, void *stream)        \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return american_enqueue<Real>(c, o, beta, seed, first, n, d_triple, pick_stream(c, stream), nullptr);\
+    }                                                                                                        \
+    extern "C" int mc_american_run_##X(mc_context *c, const mc_american_##X *o, const double *beta, uint64_t seed,\
+                                       uint64_t first, uint64_t n, mc_result *out)                           \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->option.r * (double)o->option.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return american_enqueue<Real>(c, o, beta, seed, first, n, t, st, nullptr);                       \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_american_paths_##X(mc_context *c, const mc_american_##X *o, const double *beta, uint64_t seed,\
+                                         uint64_t first, uint64_t n, Real *h_out)                            \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return american_enqueue<Real>(c, o, beta, seed, first, n, t, st, d);                             \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_american_fit_##X(mc_context *c, const mc_american_##X *o, uint64_t seed, uint64_t first, uint64_t n,\
+                                       double *beta, mc_result *in_sample)                                   \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, beta)) return rc;                                          \
+        if (!in_sample) return fail(MC_ERR_INVALID, "NULL output");                                          \
+        return american_fit<Real>(c, o, seed, first, n, beta, in_sample);                                    \
+    }                                                                                                        \
+    extern "C" int mc_american_fit_date_##X(mc_context *c, const mc_american_##X *o, int j, const double *beta_next,\
+                                            uint64_t seed, uint64_t first, uint64_t n, Real *h_W, Real *h_V, double *sums)\
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, sums)) return rc;                                          \
+        if (!beta_next || !h_W || !h_V) return fail(MC_ERR_INVALID, "NULL argument");                        \
+        return american_fit_date<Real>(c, o, j, beta_next, seed, first, n, h_W, h_V, sums);                  \
     }                                                                                                        \
     extern "C" int mc_heston_launch_##X(mc_context *c, const mc_heston_##X *o, uint64_t seed, uint64_t first,\
                                         uint64_t n, double *d_triple, void *stream)                          \

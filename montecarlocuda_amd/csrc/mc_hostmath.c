@@ -14,6 +14,8 @@
  *   mc_lookback_closed_form_* Goldman-Sosin-Gatto / Conze-Viswanathan prices of the continuously monitored lookbacks
  *   mc_merton_closed_form_*  Merton's series for the European call under the jump-diffusion; mc_merton_thresholds_* the integer
  *                            Poisson thresholds of its count draw
+ *   mc_american_solve        one date's regression of a Longstaff-Schwartz fit; mc_american_lattice_* the binomial price of the
+ *                            Bermudan put or call
  *   mc_heston_closed_form_*  exact price of the European call under the Heston model (Gauss-Legendre quadrature)
  *   mc_last_error / mc_internal_fail   the per-thread error text of whichever library this object is linked into
  */
@@ -113,6 +115,85 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
     return s * p1 - k * exp(-r * t) * p2;
 }
 
+/* One date's regression of a Longstaff-Schwartz fit (the rule is stated in mc_mi355x.h). */
+int mc_american_solve(const double *sums, int degree, double beta[4])
+{
+    if (!sums || !beta)
+        return mc_internal_fail(MC_ERR_INVALID, "american solve: NULL argument");
+    if (degree < 1 || degree > 3)
+        return mc_internal_fail(MC_ERR_INVALID, "american solve: degree=%d outside [1, 3]", degree);
+    const int n = degree + 1;
+    double d[4], l[4][4], y[4];
+    beta[0] = INFINITY, beta[1] = beta[2] = beta[3] = 0.0;
+    if (!(sums[0] >= (double)MC_AMERICAN_MIN_ITM))
+        return MC_OK;
+    for (int i = 0; i < n; ++i) {
+        if (!(sums[2 * i] > 0) || !isfinite(sums[2 * i]))
+            return MC_OK;
+        d[i] = sqrt(sums[2 * i]);
+    }
+    /* Cholesky of the scaled Gram matrix G_ik = sums[i + k] / (d_i d_k), row by row; its diagonal is 1 */
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k <= i; ++k) {
+            double acc = sums[i + k] / (d[i] * d[k]);
+            for (int q = 0; q < k; ++q)
+                acc -= l[i][q] * l[k][q];
+            if (k < i) {
+                l[i][k] = acc / l[k][k];
+            } else {
+                if (!(acc > 0))
+                    return MC_OK;
+                l[i][i] = sqrt(acc);
+            }
+        }
+    }
+    for (int i = 0; i < n; ++i) {   /* L y = b / d */
+        double acc = sums[7 + i] / d[i];
+        for (int q = 0; q < i; ++q)
+            acc -= l[i][q] * y[q];
+        y[i] = acc / l[i][i];
+    }
+    for (int i = n - 1; i >= 0; --i) {   /* L' x = y, beta = x / d */
+        double acc = y[i];
+        for (int q = i + 1; q < n; ++q)
+            acc -= l[q][i] * y[q];
+        y[i] = acc / l[i][i];
+    }
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(y[i] / d[i]))
+            return MC_OK;
+    for (int i = 0; i < n; ++i)
+        beta[i] = y[i] / d[i];
+    return MC_OK;
+}
+
+/* The Cox-Ross-Rubinstein price of the Bermudan put (q = -1) or call (q = +1) with exercise on every `every`-th of `steps` steps
+ * (mc_american_lattice_*; inputs already checked).  NaN when the risk-neutral probability leaves (0, 1) or memory runs out. */
+static double american_lattice_fp64(double s, double k, double r, double v, double t, double q, int steps, int every)
+{
+    const double h = t / (double)steps, lu = v * sqrt(h), grow = exp(r * h), u = exp(lu), dn = exp(-lu);
+    const double pu = (grow - dn) / (u - dn), disc = 1.0 / grow;
+    if (!(pu > 0 && pu < 1))
+        return NAN;
+    double *val = (double *)malloc(sizeof(double) * ((size_t)steps + 1));
+    if (!val)
+        return NAN;
+    for (int i = 0; i <= steps; ++i)   /* node i of level n: spot s exp((2 i - n) lu) */
+        val[i] = fmax(q * (s * exp((double)(2 * i - steps) * lu) - k), 0.0);
+    for (int n = steps - 1; n >= 0; --n) {
+        const int ex = n > 0 && n % every == 0;
+        for (int i = 0; i <= n; ++i) {
+            double c = disc * (pu * val[i + 1] + (1.0 - pu) * val[i]);
+            if (ex)
+                c = fmax(c, q * (s * exp((double)(2 * i - n) * lu) - k));
+            val[i] = c;
+        }
+    }
+    const double price = val[0];
+    free(val);
+    return price;
+}
+
 /* One body per precision: REAL, SQRT_R, X set by the includer below. */
 #define MC_HM_CAT_(a, b) a##_##b
 #define MC_HM_CAT(a, b) MC_HM_CAT_(a, b)
@@ -127,6 +208,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define LOOKBACK mc_lookback_f32
 #define HESTON mc_heston_f32
 #define MERTON mc_merton_f32
+#define AMERICAN mc_american_f32
 #define MERTON_BITS 32
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -138,6 +220,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef LOOKBACK
 #undef HESTON
 #undef MERTON
+#undef AMERICAN
 #undef MERTON_BITS
 
 #define REAL double
@@ -149,6 +232,7 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #define LOOKBACK mc_lookback_f64
 #define HESTON mc_heston_f64
 #define MERTON mc_merton_f64
+#define AMERICAN mc_american_f64
 #define MERTON_BITS 64
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -160,4 +244,5 @@ static double heston_call_fp64(double s, double k, double r, double t, double v0
 #undef LOOKBACK
 #undef HESTON
 #undef MERTON
+#undef AMERICAN
 #undef MERTON_BITS

@@ -16,6 +16,9 @@ int mc_lookback_check_f64(const mc_lookback_f64 *o);
 /* The input checks of the jump-diffusion calls, shared by mc_merton_closed_form_*, mc_merton_thresholds_* and the GPU entry points (not exported). */
 int mc_merton_check_f32(const mc_merton_f32 *o);
 int mc_merton_check_f64(const mc_merton_f64 *o);
+/* The input checks of the Bermudan options, shared by mc_american_lattice_* and the GPU entry points (not exported). */
+int mc_american_check_f32(const mc_american_f32 *o);
+int mc_american_check_f64(const mc_american_f64 *o);
 /* The input checks of the Heston call, shared by mc_heston_closed_form_* and the GPU entry points (not exported). */
 int mc_heston_check_f32(const mc_heston_f32 *o);
 int mc_heston_check_f64(const mc_heston_f64 *o);

@@ -382,3 +382,41 @@ int FN(mc_merton_closed_form)(const MERTON *o, double *price)
     *price = sum;
     return MC_OK;
 }
+
+/* The inputs every Bermudan entry point refuses (see mc_mi355x.h).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_american_check)(const AMERICAN *o)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, v = (double)o->option.v, t = (double)o->option.t;
+    if (o->n_dates < 1 || o->n_dates > MC_MAX_AMERICAN_DATES)
+        return mc_internal_fail(MC_ERR_INVALID, "american: n_dates=%d outside [1, %d]", o->n_dates, MC_MAX_AMERICAN_DATES);
+    if (o->type != MC_AMERICAN_PUT && o->type != MC_AMERICAN_CALL)
+        return mc_internal_fail(MC_ERR_INVALID, "american: type=%d is neither MC_AMERICAN_PUT nor MC_AMERICAN_CALL", o->type);
+    if (o->degree < 1 || o->degree > 3)
+        return mc_internal_fail(MC_ERR_INVALID, "american: degree=%d outside [1, 3]", o->degree);
+    if (!isfinite(s) || !isfinite(k) || !isfinite(r) || !isfinite(v) || !isfinite(t))
+        return mc_internal_fail(MC_ERR_INVALID, "american: need finite s, k, r, v, t");
+    if (!(s > 0) || !(k > 0) || !(t > 0) || !(v >= 0))
+        return mc_internal_fail(MC_ERR_INVALID, "american: need s>0, k>0, t>0, v>=0");
+    return MC_OK;
+}
+
+/* Discounted Cox-Ross-Rubinstein price of the Bermudan put or call (the lattice is stated in mc_mi355x.h). */
+int FN(mc_american_lattice)(const AMERICAN *o, int steps_per_date, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "american lattice: NULL argument");
+    int rc = FN(mc_american_check)(o);
+    if (rc != MC_OK)
+        return rc;
+    if (steps_per_date < 1 || (long long)steps_per_date * o->n_dates > (1 << 15))
+        return mc_internal_fail(MC_ERR_INVALID, "american lattice: n_dates * steps_per_date = %lld outside [1, %d]",
+                                (long long)steps_per_date * o->n_dates, 1 << 15);
+    if (!((double)o->option.v > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "american lattice: needs v > 0");
+    const double p = american_lattice_fp64((double)o->option.s, (double)o->option.k, (double)o->option.r, (double)o->option.v, (double)o->option.t,
+                                           o->type == MC_AMERICAN_PUT ? -1.0 : 1.0, steps_per_date * o->n_dates, steps_per_date);
+    if (!isfinite(p))
+        return mc_internal_fail(MC_ERR_INVALID, "american lattice: the risk-neutral probability leaves (0, 1): more steps per date are needed");
+    *price = p;
+    return MC_OK;
+}

@@ -2640,6 +2640,321 @@ __global__ __launch_bounds__(GROUP) void merton_kernel(const Tail /* first argum
 }
 
 // =========================================================================================
+// Bermudan put / call on m equally spaced exercise dates under a GIVEN exercise rule: the pricing pass of Longstaff-Schwartz
+// (the model is stated in mc_mi355x.h).  Not in the reference.  The walk is asian_path's -- W_j = z_1 + ... + z_j the lane's
+// only state of the walk, x_j = fma(W_j, bx, xk_j) in units of the strike -- and date j's ROW of six wave-uniform values
+//   xk_j = ln(s/k) + j a (exponent units),  g_j = exp(r (t - t_j)),  beta_j0 .. beta_j3
+// comes from the per-date table (folded in fp64, rounded once) through scalar loads.  A date costs one exponential, the payoff
+// p = max(q (e - 1), 0), three fmas of Horner C = ((b3 p + b2) p + b1) p + b0, one multiply p g, two compares and a select:
+//   ex = p > 0 && p g > C;   value = alive && ex ? p g : value;   alive &= !ex
+// alive is a lane mask: and-ed on the scalar unit.  The LAST date's row is written by the host as {-inf, 0, 0, 0}: p g > -inf
+// holds for every p > 0, so "exercise iff p_m > 0" needs no code of its own; a never-exercise row is {+inf, 0, 0, 0}.  With
+// b1 = b2 = b3 = 0 the Horner form passes +-inf through without a NaN for every finite p.
+//   ANTI: the same at -W, with its own mask and value; the mean of the two.
+// The walk always runs to maturity, also when no lane of the wave is alive any more: see DESIGN 4.13.
+// Stream: domain 12, the Asian layout.
+// =========================================================================================
+enum { AMERICAN_ROW = 6 };   // values per date in the table
+template <class Real>
+struct AmericanArgs {
+    const Real *rows;   // n_dates rows {xk, g, b0, b1, b2, b3}
+    int n_dates;
+    Real bx;            // v sqrt(dt) in exponent units
+    Real q;             // -1 put, +1 call
+};
+
+// Payoff, continuation value and decision of one date at the spot e (in units of the strike): what a fit of the rule and the
+// pricing pass must agree on to the bit.  pg = p g, the path's value if it exercises here.
+template <class Real>
+__device__ __forceinline__ bool american_decide(Real e, Real q, Real g, Real b0, Real b1, Real b2, Real b3, Real &pg)
+{
+    const Real d = fma_r(e, q, -q);
+    const Real p = d > 0 ? d : 0;
+    const Real C = fma_r(fma_r(fma_r(b3, p, b2), p, b1), p, b0);
+    pg = p * g;
+    return p > 0 && pg > C;
+}
+
+// the date's row through the constant address space: the table is written before the launch and only read here, and its loads
+// must be scalar loads whatever hipcc can prove about the stores around them (merton_count's remedy)
+template <class Real> using AmericanRowPtr = const __attribute__((address_space(4))) Real *;
+
+template <bool ANTI, class Real>
+__device__ __forceinline__ void american_date(AmericanRowPtr<Real> r, Real q, Real x, Real x_m, bool &alive, bool &alive_m, Real &val, Real &val_m)
+{
+    const Real g = r[1], b0 = r[2], b1 = r[3], b2 = r[4], b3 = r[5];
+    Real pg;
+    const bool ex = american_decide(exp_model(x), q, g, b0, b1, b2, b3, pg);
+    val = alive && ex ? pg : val;
+    alive = alive && !ex;
+    if (ANTI) {
+        const bool ex_m = american_decide(exp_model(x_m), q, g, b0, b1, b2, b3, pg);
+        val_m = alive_m && ex_m ? pg : val_m;
+        alive_m = alive_m && !ex_m;
+    }
+}
+
+// fp32: four dates per trip, one Philox block.
+template <bool ANTI, class Gen>
+__device__ __forceinline__ float american_path(Gen &gen, const AmericanArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "four dates per block");
+    const auto rows = (AmericanRowPtr<float>)o.rows;
+    const int n = o.n_dates;
+    float W = 0, val = 0, val_m = 0;
+    bool alive = true, alive_m = true;
+    float z[NPB];
+    auto date = [&](int j, float zj) {
+        W += zj;
+        const auto r = rows + AMERICAN_ROW * j;
+        const float xk = r[0];
+        american_date<ANTI>(r, o.q, __builtin_fmaf(W, o.bx, xk), __builtin_fmaf(-W, o.bx, xk), alive, alive_m, val, val_m);
+    };
+    int j0 = 0;
+    for (; j0 + NPB <= n; j0 += NPB) {
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 12u /*MC_DOMAIN_AMERICAN*/, z);
+        date(j0, z[0]);
+        date(j0 + 1, z[1]);
+        date(j0 + 2, z[2]);
+        date(j0 + 3, z[3]);
+    }
+    if (j0 < n) {   // wave-uniform: one to three dates left
+        gen.normals(w, c0, (uint32_t)(j0 / NPB), 12u /*MC_DOMAIN_AMERICAN*/, z);
+        date(j0, z[0]);
+        if (j0 + 1 < n)
+            date(j0 + 1, z[1]);
+        if (j0 + 2 < n)
+            date(j0 + 2, z[2]);
+    }
+    return ANTI ? 0.5f * (val + val_m) : val;
+}
+
+// fp64: asian_path<double>'s loop (Box-Muller pairs through the generator's pair cursor, four pairs per trip, then one).  bx (and
+// -bx for the mirrored path) sit in vector registers for the whole path, so x = fma(W, bx, xk_j) reads xk_j from its SGPR pair.
+template <bool ANTI, class Gen>
+__device__ __forceinline__ double american_path(Gen &gen, const AmericanArgs<double> &o, const Work &w, uint32_t c0)
+{
+    const auto rows = (AmericanRowPtr<double>)o.rows;
+    const int n = o.n_dates;
+    double W = 0, val = 0, val_m = 0;
+    bool alive = true, alive_m = true;
+    const double bx_v = to_vgpr(o.bx);
+    [[maybe_unused]] const double nbx_v = to_vgpr(-o.bx);
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto date = [&](int j, double zj) {
+        W += zj;
+        const auto r = rows + AMERICAN_ROW * j;
+        const double xk = r[0];
+        american_date<ANTI>(r, o.q, fma_scalar_addend(W, bx_v, xk), ANTI ? fma_scalar_addend(W, nbx_v, xk) : 0.0, alive, alive_m, val, val_m);
+    };
+    auto tie = [&](uint32_t &blk) {
+        if constexpr (ANTI)
+            asm("" : "+v"(W), "+v"(val), "+v"(val_m), "+s"(blk));
+        else
+            asm("" : "+v"(W), "+v"(val), "+s"(blk));
+    };
+    int j = 0;
+    if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+        for (; j + 8 <= n; j += 8) {
+            uint32_t blk = (uint32_t)(j >> 3);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // a pair's generator call starts after the walk of the pair before it (barrier_path<double>'s tie): left free, hipcc
+                // overlaps the exponentials of a trip and hoists the eight rows' scalar loads to its top (131 VGPRs, 21 SGPR spills)
+                if (k)
+                    tie(blk);
+                double z0, z1;
+                gen.pair(w, c0, 12u /*MC_DOMAIN_AMERICAN*/, (blk << 2) | k, carry, z0, z1);
+                const int jd = (int)(blk << 3) + 2 * (int)k;   // the rows' addresses hang on the tie: their scalar loads stay behind it
+                date(jd, z0);
+                tie(blk);   // the second date's exponential after the first's
+                date(jd + 1, z1);
+            }
+        }
+    }
+#pragma unroll 1
+    for (; j < n; j += 2) {
+        double z0, z1;
+        gen.pair(w, c0, 12u /*MC_DOMAIN_AMERICAN*/, (uint32_t)(j >> 1), carry, z0, z1);
+        date(j, z0);
+        if (j + 1 < n)   // wave-uniform
+            date(j + 1, z1);
+    }
+    gen.pairs_done((uint32_t)((n + 1) >> 1));
+    return ANTI ? 0.5 * (val + val_m) : val;
+}
+
+// one lane per path, grid-stride over the segment's paths: asian_kernel's frame
+template <class Real, bool ANTI, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void american_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const AmericanArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = american_path<ANTI>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
+// The Longstaff-Schwartz FIT of that rule: the first product here whose paths are not independent -- a date's rule is a regression
+// over all paths -- so the fit is one launch per date, j = m ... 0, with the per-path state (W, V) in global memory between them.
+// The walk runs BACKWARD without storing the path: W_m = sqrt(m) z_m, W_j = j/(j+1) W_{j+1} + sqrt(j/(j+1)) z_j is the Brownian
+// bridge from 0, exact in law (the host passes cw = j/(j+1), cz = sqrt(j/(j+1)); j = m: cw = 0, cz = sqrt(m)).  Launch j, lane = path:
+//   load (W_{j+1}, V);  j + 1 < m: apply date j + 1's decision with row j + 1 of the device table (american_decide, the pricing
+//   pass's own), V = ex ? p g : V;  draw z_j, step to W_j, p_j = payoff at W_j;  j = m: V = p_m;  store (W_j, V);
+//   0 < j < m and p_j > 0: add p_j^k, k = 0 .. 6, and p_j^k V, k = 0 .. 3, in fp64;   j = 0: add V and V^2.
+// The twelve sums leave as six (s, q) pairs, one per plane of the call's pair buffer, the way vanilla_greeks_kernel's do; the last
+// workgroup writes them as six triples {sums[2 i], sums[2 i + 1], n}.  american_solve_kernel, one lane between two date launches,
+// reads them, solves the date's normal equations (mc_american_solve's arithmetic, operation for operation, contraction off) and writes row
+// j of the table, rounded once to Real, and an fp64 copy for the host: all 2 m + 1 launches go on the stream without a host
+// synchronisation in between.  Stream: domain 13, the Asian layout (a date draws one entry of its block; the rest is dead code).
+// =========================================================================================
+enum { AMERICAN_FIT_PLANES = 6 };
+template <class Real>
+struct AmericanFitArgs {
+    Real *W, *V;         // the state of the launch's first path
+    const Real *rows;    // the device table: n_dates rows {xk, g, b0 .. b3}; american_solve_kernel writes the b's
+    int j, n_dates;      // the date this launch walks TO
+    Real bx, q;
+    Real cw, cz;         // W_j = cw W_{j+1} + cz z_j
+};
+
+template <class Real, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void american_fit_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const AmericanFitArgs<Real> o, const Work w)
+{
+    stage_tables<Real>();
+    constexpr int NPB = Gen::template npb<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc[2 * AMERICAN_FIT_PLANES] = {};
+    Gen gen(w);
+    const auto rows = (AmericanRowPtr<Real>)o.rows;
+    const int j = o.j, m = o.n_dates;   // wave-uniform: every branch on them is a scalar branch
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        Real W = 0, V = 0;
+        if (j < m) {
+            W = o.W[i], V = o.V[i];
+            if (j + 1 < m) {   // date j + 1's decision, with the rule the solve between the two launches wrote
+                const auto r = rows + AMERICAN_ROW * j;
+                Real pg;
+                const bool ex = american_decide(exp_model(fma_r(W, o.bx, r[0])), o.q, r[1], r[2], r[3], r[4], r[5], pg);
+                V = ex ? pg : V;
+            }
+        }
+        if (j == 0) {
+            pair_add(acc, 0, (double)V);
+            continue;
+        }
+        Real z[NPB];
+        gen.normals(w, w.unit_lo + i, (uint32_t)(j - 1) / NPB, 13u /*MC_DOMAIN_AMERICAN_FIT*/, z);
+        Real zj = z[0];
+#pragma unroll
+        for (int e = 1; e < NPB; ++e)   // a select chain on a wave-uniform index: no indexed register array
+            zj = (j - 1) % NPB == e ? z[e] : zj;
+        W = fma_r(o.cw, W, o.cz * zj);
+        const Real d = fma_r(exp_model(fma_r(W, o.bx, rows[AMERICAN_ROW * (j - 1)])), o.q, -o.q);
+        const Real p = d > 0 ? d : 0;
+        if (j == m)
+            V = p;
+        o.W[i] = W, o.V[i] = V;
+        if (j < m && p > 0) {
+            const double p1 = (double)p, v = (double)V, p2 = p1 * p1, p3 = p2 * p1;
+            acc[0] += 1.0, acc[1] += p1, acc[2] += p2, acc[3] += p3, acc[4] += p2 * p2, acc[5] += p2 * p3, acc[6] += p3 * p3;
+            acc[7] += v, acc[8] += p1 * v, acc[9] += p2 * v, acc[10] += p3 * v;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < AMERICAN_FIT_PLANES; ++q) {
+        group_sum2(acc[2 * q], acc[2 * q + 1]);
+        pair_publish(late_tail(acc[2 * q]), acc, q, q);
+    }
+    arrive_and_finish(late_tail(acc[0]));
+}
+
+// sums[i] of mc_american_solve from the six triples of a date launch
+__device__ __forceinline__ double american_sum(const double *triples, int i) { return triples[3 * (i >> 1) + (i & 1)]; }
+
+// One lane.  mc_american_solve (mc_hostmath.c) restated for the device, operation for operation, with contraction off.  Equal bits
+// with the host are not claimed: that would also need the device's fp64 division and root correctly rounded, and no test feeds one
+// set of sums through both (the whole fit is compared with the float64 model within 16 times the model's own movement).
+template <class Real, int DEGREE>
+__global__ void american_solve_kernel(const double *__restrict__ triples, Real *__restrict__ row_beta, double *__restrict__ beta64)
+{
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0 || blockIdx.x != 0)
+        return;
+    constexpr int N = DEGREE + 1;
+    double beta[4] = {__builtin_inf(), 0.0, 0.0, 0.0};
+    double d[N], l[N][N], y[N];
+    bool ok = american_sum(triples, 0) >= 32.0 /*MC_AMERICAN_MIN_ITM*/;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double a = american_sum(triples, 2 * i);
+        ok = ok && a > 0 && a < __builtin_inf();
+        d[i] = __builtin_sqrt(ok ? a : 1.0);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int k = 0; k <= i; ++k) {
+            double a = american_sum(triples, i + k) / (d[i] * d[k]);
+#pragma unroll
+            for (int c = 0; c < k; ++c)
+                a -= l[i][c] * l[k][c];
+            if (k < i) {
+                l[i][k] = a / l[k][k];
+            } else {
+                ok = ok && a > 0;
+                l[i][i] = __builtin_sqrt(ok ? a : 1.0);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double a = american_sum(triples, 7 + i) / d[i];
+#pragma unroll
+        for (int c = 0; c < i; ++c)
+            a -= l[i][c] * y[c];
+        y[i] = a / l[i][i];
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double a = y[i];
+#pragma unroll
+        for (int c = i + 1; c < N; ++c)
+            a -= l[c][i] * y[c];
+        y[i] = a / l[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        y[i] = y[i] / d[i];
+        ok = ok && __builtin_fabs(y[i]) < __builtin_inf();
+    }
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            beta[i] = y[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        row_beta[i] = (Real)beta[i];
+        beta64[i] = beta[i];
+    }
+}
+
+// =========================================================================================
 // European call under the Heston stochastic-volatility model, full-truncation Euler in log space on m equal steps (the model
 // is stated in mc_mi355x.h).  Not in the reference.  The first walk here whose step is non-linear in its state: besides the
 // normals a lane carries the variance V and two running sums, because

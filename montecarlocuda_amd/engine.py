@@ -166,6 +166,28 @@ def _as_merton(X, o, jumps=None, n_dates=None, payoff=None, barrier=None, kind=N
                           0.0 if barrier is None else float(barrier))
 
 
+def _as_american(X, o, n_dates=None, kind=None, degree=None) -> C.Structure:
+    """mc_american_*: an option (OptionData or dict) with n_dates, the kind ("put" or "call") and the degree of a fit's
+    polynomial, or a dict that carries "n_dates" and optionally "kind" and "degree" itself."""
+    if n_dates is None:
+        n_dates, kind, degree = o["n_dates"], o.get("kind", "put"), o.get("degree", 3)
+    kind = _lib.AMERICAN_TYPES[kind] if isinstance(kind, str) else int(kind)
+    return _lib.AMERICAN[X](_as_option(X, o), int(n_dates), kind, 3 if degree is None else int(degree))
+
+
+class _AmericanHolder:
+    """The contract's struct with its exercise rule: an (n_dates, 4) float64 array kept alive for as long as the struct is in use."""
+
+    def __init__(self, X, o, beta, n_dates=None, kind=None, degree=None):
+        if beta is None:
+            beta = o["beta"]
+        self.struct = _as_american(X, o, n_dates, kind, degree)
+        self.beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if self.beta.shape != (self.struct.n_dates, 4):
+            raise ValueError(f"beta has shape {self.beta.shape}, expected ({self.struct.n_dates}, 4)")
+        self.beta_ptr = self.beta.ctypes.data_as(C.POINTER(C.c_double))
+
+
 def _estimate(r: _lib.Result) -> Estimate:
     return Estimate(r.expected, r.confidence, r.sum, r.sum2, int(r.n), float(r.kernel_ms), float(r.wall_ms))
 
@@ -459,10 +481,45 @@ class Engine:
         kind as for barrier(); there is no continuous monitoring."""
         return self._run("merton", precision, _as_merton(precision, opt, jumps, n_dates, "barrier", barrier, kind), seed, first_path, n_paths)
 
+    def american(self, opt, n_dates, beta, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="put") -> Estimate:
+        """Bermudan put or call on n_dates equally spaced exercise dates under the exercise rule beta, an (n_dates, 4) table of
+        cubics in the payoff (mc_american_run_*): a lower bound of the price when beta was not fitted on these paths.  Honours
+        set_antithetic."""
+        h = _AmericanHolder(precision, opt, beta, n_dates, kind)
+        r = _lib.Result()
+        check(getattr(lib(), f"mc_american_run_{precision}")(self._ctx, C.byref(h.struct), h.beta_ptr, seed, first_path, n_paths, C.byref(r)))
+        return _estimate(r)
+
+    def american_fit(self, opt, n_dates, n_paths, kind="put", degree=3, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        """The exercise rule of a Bermudan put or call by Longstaff-Schwartz on n_paths (<= 2^24) paths of their own
+        (mc_american_fit_*): (beta, Estimate), beta the (n_dates, 4) table american() prices, the Estimate the in-sample one
+        (biased high)."""
+        s = _as_american(precision, opt, n_dates, kind, degree)
+        beta = np.zeros((min(max(int(n_dates), 1), _lib.MAX_AMERICAN_DATES), 4), dtype=np.float64)   # an n_dates out of range is refused before beta is written
+        r = _lib.Result()
+        check(getattr(lib(), f"mc_american_fit_{precision}")(self._ctx, C.byref(s), seed, first_path, n_paths,
+                                                              beta.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return beta, _estimate(r)
+
+    def american_fit_date(self, opt, n_dates, j, W, V, beta_next, kind="put", degree=3, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        """Test hook (mc_american_fit_date_*): one date launch of the fit on the state (W, V) of date j + 1; returns (W_j, V, sums)."""
+        s = _as_american(precision, opt, n_dates, kind, degree)
+        W, V = np.array(W, dtype=NP[precision]), np.array(V, dtype=NP[precision])
+        b = np.ascontiguousarray(beta_next, dtype=np.float64)
+        sums = np.zeros(12, dtype=np.float64)
+        RP, DP = C.POINTER(_lib.CT[precision]), C.POINTER(C.c_double)
+        check(getattr(lib(), f"mc_american_fit_date_{precision}")(self._ctx, C.byref(s), int(j), b.ctypes.data_as(DP), seed, first_path, W.size,
+                                                                   W.ctypes.data_as(RP), V.ctypes.data_as(RP), sums.ctypes.data_as(DP)))
+        return W, V, sums
+
     # ---- asynchronous launches (device triple, caller's stream) ------------------------
     def launch(self, prod, precision, struct, seed, first_path, n_paths, d_triple_ptr: int, stream: int = 0):
         """Enqueue; d_triple_ptr = device address of 3 doubles, stream = hipStream_t handle (0 = the HIP null
         stream; ``self.stream`` is the context's own)."""
+        if prod == "american":   # struct: what prepared("american", ...) returned, the contract with its rule
+            check(getattr(lib(), f"mc_american_launch_{precision}")(self._ctx, C.byref(struct.struct), struct.beta_ptr, seed, first_path,
+                                                                     n_paths, C.c_void_p(d_triple_ptr), C.c_void_p(stream)))
+            return
         check(getattr(lib(), f"mc_{prod}_launch_{precision}")(self._ctx, C.byref(struct), seed, first_path,
                                                                n_paths, C.c_void_p(d_triple_ptr),
                                                                C.c_void_p(stream)))
@@ -480,6 +537,9 @@ class Engine:
             return _as_heston(precision, inputs), None
         if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
             return _as_heston_path(precision, inputs), None
+        if prod == "american":   # inputs: the option's fields plus "n_dates", "beta" and optionally "kind", "degree"
+            h = _AmericanHolder(precision, inputs, None)
+            return h, h
         if prod == "merton":   # inputs: the option's fields plus "lambda", "mu_j", "delta", "n_dates" and optionally "payoff", "barrier", "kind"
             return _as_merton(precision, inputs), None
         if prod == "lookback":   # inputs: the option's fields plus "n_dates" and optionally "kind", "monitoring"
@@ -524,6 +584,14 @@ class Engine:
 
     def merton_barrier_paths(self, opt, jumps, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out"):
         return self._paths("merton", precision, _as_merton(precision, opt, jumps, n_dates, "barrier", barrier, kind), seed, first_path, n_paths)
+
+    def american_paths(self, opt, n_dates, beta, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="put"):
+        """The per-path values of american(): in units of the strike, compounded to maturity."""
+        h = _AmericanHolder(precision, opt, beta, n_dates, kind)
+        out = np.empty(n_paths, dtype=NP[precision])
+        check(getattr(lib(), f"mc_american_paths_{precision}")(self._ctx, C.byref(h.struct), h.beta_ptr, seed, first_path, n_paths,
+                                                                out.ctypes.data_as(C.POINTER(_lib.CT[precision]))))
+        return out
 
     def heston_paths(self, opt, model, n_steps, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         return self._paths("heston", precision, _as_heston(precision, opt, model, n_steps), seed, first_path, n_paths)
@@ -676,6 +744,25 @@ def merton_thresholds(opt, jumps, n_dates, precision="f64"):
     check(getattr(lib(), f"mc_merton_thresholds_{precision}")(C.byref(_as_merton(precision, opt, jumps, n_dates, "european")),
                                                                out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
     return out[:n.value].copy()
+
+
+def american_solve(sums, degree=3):
+    """One date's regression of a Longstaff-Schwartz fit (mc_american_solve): sums = [sum p^k, k = 0..6; sum p^k V, k = 0..3]
+    over the paths in the money; the four coefficients of the continuation value, or [inf, 0, 0, 0] ("never exercise")."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.shape != (_lib.AMERICAN_SUMS,):
+        raise ValueError(f"sums has shape {sums.shape}, expected ({_lib.AMERICAN_SUMS},)")
+    beta = np.empty(4, dtype=np.float64)
+    check(lib().mc_american_solve(sums.ctypes.data_as(C.POINTER(C.c_double)), int(degree), beta.ctypes.data_as(C.POINTER(C.c_double))))
+    return beta
+
+
+def american_lattice(opt, n_dates, steps_per_date, kind="put", precision="f64"):
+    """Discounted Cox-Ross-Rubinstein price of the Bermudan put or call with exercise on the n_dates dates only, on
+    n_dates * steps_per_date steps (mc_american_lattice_*; fp64, no GPU)."""
+    p = C.c_double()
+    check(getattr(lib(), f"mc_american_lattice_{precision}")(C.byref(_as_american(precision, opt, n_dates, kind, 3)), int(steps_per_date), C.byref(p)))
+    return p.value
 
 
 def heston_closed_form(opt, model, precision="f64"):
