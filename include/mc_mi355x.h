@@ -77,6 +77,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_MERTON_JUMPS 11u /* the jump-diffusion's Poisson counts: raw Philox blocks, see mc_merton_run_* */
 #define MC_DOMAIN_AMERICAN 12u /* the pricing pass of the Bermudan options, see mc_american_run_* */
 #define MC_DOMAIN_AMERICAN_FIT 13u /* the fit of their exercise rule, see mc_american_fit_*: never the paths the rule is priced on */
+#define MC_DOMAIN_RAINBOW 14u /* worst-of / best-of options on a correlated basket walked over dates, see mc_rainbow_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -173,6 +174,21 @@ typedef struct { mc_option_f64 option; double lambda, mu_j, delta; int n_dates, 
 enum { MC_AMERICAN_PUT = 0, MC_AMERICAN_CALL = 1 };
 typedef struct { mc_option_f32 option; int n_dates, type, degree; } mc_american_f32;
 typedef struct { mc_option_f64 option; int n_dates, type, degree; } mc_american_f64;
+
+/* Worst-of / best-of ("rainbow") option on basket.n correlated assets, 1 <= n <= MC_MAX_RAINBOW_ASSETS, walked over n_dates
+ * equally spaced dates t_j = j t / n_dates, j = 1 ... n_dates, with an optional barrier on the same extremum (see
+ * mc_rainbow_run_*).  Not in the reference.  basket.s, v, p and w are read as mc_basket_run_* reads them (p the row-major
+ * lower-triangular Cholesky factor of the correlation; only its lower triangle is read); basket.k, t and r are the contract's
+ * strike, maturity and rate.  basket.d, the reference's shift of the terminal normals, has no meaning on a walk: NULL or all
+ * zeros.  type is one of MC_RAINBOW_*; barrier_type is MC_RAINBOW_NO_BARRIER (barrier is then ignored) or one of MC_BARRIER_*.
+ * The per-date constants travel as a table of n values per date, folded in fp64 and rounded once, read through scalar loads:
+ * the cap on n n_dates keeps that table (16 KB in fp32, 32 KB in fp64) the size of the scalar data cache, as the Asian call's. */
+#define MC_MAX_RAINBOW_ASSETS 8
+#define MC_MAX_RAINBOW_TABLE 4096   /* n * n_dates at most */
+enum { MC_RAINBOW_CALL_ON_MIN = 0, MC_RAINBOW_CALL_ON_MAX = 1, MC_RAINBOW_PUT_ON_MIN = 2, MC_RAINBOW_PUT_ON_MAX = 3 };
+enum { MC_RAINBOW_NO_BARRIER = -1 };
+typedef struct { mc_basket_f32 basket; float barrier; int n_dates, type, barrier_type; } mc_rainbow_f32;
+typedef struct { mc_basket_f64 basket; double barrier; int n_dates, type, barrier_type; } mc_rainbow_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -674,6 +690,64 @@ int mc_american_fit_f64(mc_context *ctx, const mc_american_f64 *opt, uint64_t se
 int mc_american_solve(const double *sums, int degree, double beta[4]);
 int mc_american_lattice_f32(const mc_american_f32 *opt, int steps_per_date, double *price);
 int mc_american_lattice_f64(const mc_american_f64 *opt, int steps_per_date, double *price);
+
+/* ---- worst-of / best-of options on a correlated basket walked over dates -----------------------------------
+ * n assets, m = n_dates dates, L = basket.p (lower triangle), z_{j,k} the standard normal of date j and factor k:
+ *   dt = t/m,  a_i = (r - v_i^2/2) dt,  M = diag(v_i sqrt(dt)) L  (lower triangle, folded in fp64, rounded once)
+ *   W_k(j) = z_{1,k} + ... + z_{j,k}
+ *   y_i(j) = ln(w_i s_i) + j a_i + sum_{k<=i} M_ik W_k(j)                the log of the weighted level of asset i on date j
+ *   e = -1 for the min types, +1 for the max types:  Y(j) = max_i e y_i(j),  X_j = exp(e Y(j))   (the worst / best weighted level)
+ *   q = +1 call, -1 put:   payoff = max(q (X_m - k), 0)
+ *   barrier, on the SAME extremum, on the dates 1 ... m only (t_0 is not monitored), a touch counts as a hit:
+ *     b = +1 up, -1 down:   d_j = b (ln barrier - e Y(j)),   P = [min_{1<=j<=m} d_j > 0]  taken by a select
+ *     value = (c0 + c1 P) payoff,  (c0, c1) = (0, 1) knock-out, (1, -1) knock-in, (1, 0) without a barrier
+ *   antithetic: the mean of the value at z and at -z
+ * The per-date constants e (ln(w_i s_i) + j a_i) are folded in fp64 and rounded once.  w_i = 1/s_i gives performance levels,
+ * w_i = 1 absolute ones.  Worst-of knock-in put: MC_RAINBOW_PUT_ON_MIN with MC_BARRIER_DOWN_IN; worst-of knock-out call:
+ * MC_RAINBOW_CALL_ON_MIN with MC_BARRIER_DOWN_OUT; best-of call: MC_RAINBOW_CALL_ON_MAX, with or without MC_BARRIER_UP_OUT.  All
+ * four types combine with all five barrier choices.  v_i = 0 is valid.
+ *
+ * Stream: path p is unit p of MC_DOMAIN_RAINBOW.  The normal of date j (1-based) and factor k (0-based) is FLAT entry
+ * (j - 1) n + k of the Asian layout: entry % npb of block entry / npb (npb = 4 in f32, 8 in f64).  No normal is drawn and
+ * dropped between two dates, whatever n is.
+ *
+ * mc_rainbow_run_* fills expected with exp(-r t) mean(value); mc_rainbow_launch_* is the asynchronous form (device triple, then
+ * mc_closing with the discount exp(-r t); several GPUs: mc_shard_range per device).  mc_rainbow_paths_* returns the per-path
+ * values (undiscounted; n_paths <= 2^26).
+ *
+ * mc_rainbow_closed_form_*: the discounted price of the contract WITHOUT a barrier at n = 1 (Black-Scholes) and n = 2 (fp64,
+ * plain C, no GPU; ignores n_dates).  L must be the factor of a CORRELATION matrix: a row whose length differs from 1 by more than
+ * fp32 rounding (|L_i0^2 + L_i1^2 - 1| > 1e-5) is refused, since the walk takes L as given and the formulas would price another
+ * model.  With S_i = w_i s_i, rho = L_10 L_00 (divided by the second row's length) and sigma^2 = v_1^2 + v_2^2 - 2 rho v_1 v_2, the call on
+ * the minimum is Stulz's formula
+ *   S_1 M(y_1, -d; -rho_1) + S_2 M(y_2, d - sigma sqrt t; -rho_2) - k e^{-rt} M(y_1 - v_1 sqrt t, y_2 - v_2 sqrt t; rho),
+ *   y_i = (ln(S_i/k) + (r + v_i^2/2) t)/(v_i sqrt t),  d = (ln(S_1/S_2) + sigma^2 t/2)/(sigma sqrt t),
+ *   rho_1 = (v_1 - rho v_2)/sigma,  rho_2 = (v_2 - rho v_1)/sigma,
+ * M the bivariate normal distribution function (Genz's Gauss-Legendre form of Drezner-Wesolowsky, 20 points); the call on the
+ * maximum is the two Black-Scholes calls minus it; the puts follow by parity with PV(min) = S_1 - Margrabe(S_1 -> S_2) and
+ * PV(max) = S_2 + Margrabe.  It needs k > 0, v_1 > 0, v_2 > 0, sigma sqrt t >= 1e-8 and sigma >= 1e-3 (v_1 + v_2) (MC_ERR_INVALID
+ * otherwise: the two assets then move as one); |rho| up to 1 is handled.  Measured against a 30-digit evaluation on five markets
+ * of three strikes (r < 0, rho < 0, |rho| = 0.95 and 0.999, levels 1 : 40): within 3.3e-16 max(S_1, S_2); the bound to rely on is
+ * 1e-10 max(S_1, S_2).
+ * MC_ERR_INVALID for n > 2 and for a barrier_type other than MC_RAINBOW_NO_BARRIER.
+ *
+ * MC_ERR_INVALID before anything is enqueued: n outside [1, MC_MAX_RAINBOW_ASSETS]; n_dates < 1; n n_dates >
+ * MC_MAX_RAINBOW_TABLE; type or barrier_type out of range; s_i <= 0, w_i <= 0, v_i < 0, t <= 0 or a non-finite input; with a
+ * barrier, barrier <= 0 or the initial extremum of w_i s_i not strictly on the live side of it (up: >= barrier, down: <=
+ * barrier); a nonzero basket.d; the control variate switched on (there is none); the range errors of the other products.
+ * MC_ERR_UNSUPPORTED: a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a context set up for external normals or the launch
+ * geometry.  The context stays usable.  Not offered: continuous monitoring, unequal dates, per-asset barriers, autocall and
+ * coupon schedules, Asian and lookback payoffs on the basket, Greeks, n > 8. */
+int mc_rainbow_run_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_rainbow_run_f64(mc_context *ctx, const mc_rainbow_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_rainbow_launch_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                          double *d_triple, void *stream);
+int mc_rainbow_launch_f64(mc_context *ctx, const mc_rainbow_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                          double *d_triple, void *stream);
+int mc_rainbow_paths_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_rainbow_paths_f64(mc_context *ctx, const mc_rainbow_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_rainbow_closed_form_f32(const mc_rainbow_f32 *opt, double *price);
+int mc_rainbow_closed_form_f64(const mc_rainbow_f64 *opt, double *price);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

@@ -30,6 +30,11 @@ MAX_AMERICAN_DATES = 512   # MC_MAX_AMERICAN_DATES
 AMERICAN_MIN_ITM = 32   # MC_AMERICAN_MIN_ITM
 AMERICAN_SUMS = 11   # MC_AMERICAN_SUMS
 AMERICAN_TYPES = {"put": 0, "call": 1}   # MC_AMERICAN_PUT, MC_AMERICAN_CALL
+DOMAIN_RAINBOW = 14   # the worst-of / best-of options: flat (date, factor) entries of the Asian layout
+MAX_RAINBOW_ASSETS = 8   # MC_MAX_RAINBOW_ASSETS
+MAX_RAINBOW_TABLE = 4096   # MC_MAX_RAINBOW_TABLE: n * n_dates at most
+RAINBOW_TYPES = {"call-on-min": 0, "call-on-max": 1, "put-on-min": 2, "put-on-max": 3}   # MC_RAINBOW_CALL_ON_MIN ... MC_RAINBOW_PUT_ON_MAX
+RAINBOW_NO_BARRIER = -1   # MC_RAINBOW_NO_BARRIER
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
 LOOKBACK_TYPES = {"floating-call": 0, "floating-put": 1, "fixed-call": 2, "fixed-put": 3}   # MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
@@ -133,6 +138,14 @@ class HestonPathF64(C.Structure):   # mc_heston_path_f64
     _fields_ = [("heston", HestonF64), ("steps_per_date", C.c_int), ("payoff", C.c_int), ("barrier_type", C.c_int), ("barrier", C.c_double)]
 
 
+class RainbowF32(C.Structure):   # mc_rainbow_f32
+    _fields_ = [("basket", BasketF32), ("barrier", C.c_float), ("n_dates", C.c_int), ("type", C.c_int), ("barrier_type", C.c_int)]
+
+
+class RainbowF64(C.Structure):   # mc_rainbow_f64
+    _fields_ = [("basket", BasketF64), ("barrier", C.c_double), ("n_dates", C.c_int), ("type", C.c_int), ("barrier_type", C.c_int)]
+
+
 class Result(C.Structure):
     _fields_ = [("expected", C.c_double), ("confidence", C.c_double), ("sum", C.c_double), ("sum2", C.c_double),
                 ("n", C.c_uint64), ("kernel_ms", C.c_float), ("wall_ms", C.c_float)]
@@ -175,6 +188,7 @@ HESTON = {"f32": HestonF32, "f64": HestonF64}
 MERTON = {"f32": MertonF32, "f64": MertonF64}
 AMERICAN = {"f32": AmericanF32, "f64": AmericanF64}
 HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
+RAINBOW = {"f32": RainbowF32, "f64": RainbowF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
@@ -198,6 +212,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
+    EXPORTS += [f"mc_rainbow_run_{_x}", f"mc_rainbow_launch_{_x}", f"mc_rainbow_paths_{_x}", f"mc_rainbow_closed_form_{_x}"]
     EXPORTS += [f"mc_merton_run_{_x}", f"mc_merton_launch_{_x}", f"mc_merton_paths_{_x}", f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}"]
     EXPORTS += [f"mc_american_run_{_x}", f"mc_american_launch_{_x}", f"mc_american_paths_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
     TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
@@ -289,6 +304,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_lookback_run_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_lookback_paths_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, RP]
         getattr(L, f"mc_lookback_closed_form_{X}").argtypes = [C.POINTER(LOOKBACK[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_rainbow_launch_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_rainbow_run_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_rainbow_paths_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_rainbow_closed_form_{X}").argtypes = [C.POINTER(RAINBOW[X]), C.POINTER(C.c_double)]
         getattr(L, f"mc_merton_launch_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_merton_run_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_merton_paths_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, RP]

@@ -85,7 +85,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a rainbow option's per-date rows, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
     void *fit_state = nullptr;    // a Longstaff-Schwartz fit's per-path state (W, V), its device table and the fp64 copy of beta: grown on demand
     size_t fit_state_bytes = 0;
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
@@ -2312,6 +2312,106 @@ static int barrier_enqueue(mc_context *c, const typename BarrierIn<Real>::type *
 }
 
 // ---------------------------------------------------------------------------------------
+// Worst-of / best-of options on a correlated basket walked over dates: rainbow_kernel, one lane per path
+// ---------------------------------------------------------------------------------------
+template <class Real> struct RainbowIn;
+template <> struct RainbowIn<float> { using type = mc_rainbow_f32; };
+template <> struct RainbowIn<double> { using type = mc_rainbow_f64; };
+static int rainbow_check(const mc_rainbow_f32 &o) { return mc_rainbow_check_f32(&o, 1); }
+static int rainbow_check(const mc_rainbow_f64 &o) { return mc_rainbow_check_f64(&o, 1); }
+
+// The range check, the constants folded in fp64 and rounded once, and the per-date table tab_ji = e (ln(w_i s_i) + j a_i)
+// (natural-log units), j = 1 ... n_dates, i = 0 ... NA - 1, in the context's table buffer: cached by content, uploaded only when
+// the inputs change.  Minimum or maximum lives in the table and in the sign of me; the barrier's direction in (g, bl); knock-in /
+// knock-out in (c0, c1); call or put in q.
+template <class Real, int NA>
+static int rainbow_table_ready(mc_context *c, const typename RainbowIn<Real>::type *v, hipStream_t st, RainbowArgs<Real, NA> &args)
+{
+    const auto &o = v->basket;
+    const double m = (double)v->n_dates, dt = (double)o.t / m, sdt = std::sqrt(dt);
+    const double e = v->type == MC_RAINBOW_CALL_ON_MAX || v->type == MC_RAINBOW_PUT_ON_MAX ? 1.0 : -1.0;
+    const double q = v->type <= MC_RAINBOW_CALL_ON_MAX ? 1.0 : -1.0;
+    const bool has_barrier = v->barrier_type != MC_RAINBOW_NO_BARRIER;
+    const double ln_b = has_barrier ? std::log((double)v->barrier) : 0.0;
+    static thread_local std::vector<Real> tab;
+    tab.resize((size_t)v->n_dates * NA);
+    for (int i = 0; i < NA; ++i) {
+        const double vi = (double)o.v[i], a = ((double)o.r - 0.5 * vi * vi) * dt, ln_s = std::log((double)o.w[i] * (double)o.s[i]);
+        double row = 0;
+        for (int k = 0; k <= i; ++k) {
+            const double mik = vi * sdt * (double)o.p[i * NA + k];
+            args.me[i * (i + 1) / 2 + k] = (Real)(e * mik);
+            row += std::fabs(mik);
+        }
+        // as for the barrier call: only the hard limit of the device's exp is enforced; below it an honest overflow of the level gives inf
+        if (!(std::fabs(ln_s) + std::fabs(ln_b) + m * (std::fabs(a) + row * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+            return fail(MC_ERR_INVALID, "rainbow: drift and volatility put the simulated level of asset %d outside the range of a double", i);
+        for (int j = 1; j <= v->n_dates; ++j)
+            tab[(size_t)(j - 1) * NA + i] = (Real)(e * (ln_s + (double)j * a));
+    }
+    if (int rc = c->table.upload(c, st, table_key(tab, 'W'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    const bool in = v->barrier_type == MC_BARRIER_UP_IN || v->barrier_type == MC_BARRIER_DOWN_IN;
+    const double b = v->barrier_type <= MC_BARRIER_UP_IN ? 1.0 : -1.0;
+    args.tab = (const Real *)c->table.d;
+    args.n_dates = v->n_dates;
+    args.g = has_barrier ? (Real)(-b * e) : (Real)0;
+    args.bl = has_barrier ? (Real)(b * ln_b) : (Real)0;
+    args.esc = (Real)(e * exp_scale<Real>());
+    args.q = (Real)q;
+    args.strike = o.k;
+    args.c0 = !has_barrier || in ? (Real)1 : (Real)0;
+    args.c1 = !has_barrier ? (Real)0 : in ? (Real)-1 : (Real)1;
+    return MC_OK;
+}
+
+template <class Real, int NA>
+static int rainbow_enqueue_n(mc_context *c, const typename RainbowIn<Real>::type *v, uint64_t seed, uint64_t n, double *d_triple, hipStream_t st,
+                             Real *out, const std::vector<Segment> &segs)
+{
+    RainbowArgs<Real, NA> args;
+    if (int rc = rainbow_table_ready<Real, NA>(c, v, st, args)) return rc;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) launch_sim(prof, rainbow_kernel<Real, NA, true>, g, st, t, args, w, dst);
+            else               launch_sim(prof, rainbow_kernel<Real, NA, false>, g, st, t, args, w, dst);
+            return MC_OK;
+        });
+}
+
+template <class Real>
+static int rainbow_enqueue(mc_context *c, const typename RainbowIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                           double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "rainbow: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "rainbow: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "rainbow: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_INVALID, "rainbow: no control variate");
+    if (int rc = rainbow_check(*v)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    switch (v->basket.n) {
+    case 1: return rainbow_enqueue_n<Real, 1>(c, v, seed, n, d_triple, st, out, segs);
+    case 2: return rainbow_enqueue_n<Real, 2>(c, v, seed, n, d_triple, st, out, segs);
+    case 3: return rainbow_enqueue_n<Real, 3>(c, v, seed, n, d_triple, st, out, segs);
+    case 4: return rainbow_enqueue_n<Real, 4>(c, v, seed, n, d_triple, st, out, segs);
+    case 5: return rainbow_enqueue_n<Real, 5>(c, v, seed, n, d_triple, st, out, segs);
+    case 6: return rainbow_enqueue_n<Real, 6>(c, v, seed, n, d_triple, st, out, segs);
+    case 7: return rainbow_enqueue_n<Real, 7>(c, v, seed, n, d_triple, st, out, segs);
+    default: return rainbow_enqueue_n<Real, 8>(c, v, seed, n, d_triple, st, out, segs);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Lookback options, discrete or Brownian-bridge continuous extrema: lookback_kernel, one lane per path
 // ---------------------------------------------------------------------------------------
 template <class Real> struct LookbackIn;
@@ -3746,6 +3846,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return barrier_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_rainbow_launch_##X(mc_context *c, const mc_rainbow_##X *o, uint64_t seed, uint64_t first,\
+                                         uint64_t n, double *d_triple, void *stream)                         \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return rainbow_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);       \
+    }                                                                                                        \
+    extern "C" int mc_rainbow_run_##X(mc_context *c, const mc_rainbow_##X *o, uint64_t seed, uint64_t first, \
+                                      uint64_t n, mc_result *out)                                            \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        const double disc = std::exp(-(double)o->basket.r * (double)o->basket.t);                            \
+        return run_sync(c, n, disc, out, [&](hipStream_t st, double *t) {                                    \
+            return rainbow_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                              \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_rainbow_paths_##X(mc_context *c, const mc_rainbow_##X *o, uint64_t seed, uint64_t first,\
+                                        uint64_t n, Real *h_out)                                             \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return rainbow_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_lookback_launch_##X(mc_context *c, const mc_lookback_##X *o, uint64_t seed, uint64_t first,\

@@ -10,6 +10,9 @@ int mc_internal_fail(int code, const char *fmt, ...) __attribute__((format(print
 /* The input checks of the barrier call, shared by mc_barrier_closed_form_* and the GPU entry points (not exported). */
 int mc_barrier_check_f32(const mc_barrier_f32 *o, int need_vol);
 int mc_barrier_check_f64(const mc_barrier_f64 *o, int need_vol);
+/* The input checks of the rainbow options, shared by mc_rainbow_closed_form_* (with_dates = 0) and the GPU entry points (not exported). */
+int mc_rainbow_check_f32(const mc_rainbow_f32 *o, int with_dates);
+int mc_rainbow_check_f64(const mc_rainbow_f64 *o, int with_dates);
 /* The input checks of the lookback options, shared by mc_lookback_closed_form_* and the GPU entry points (not exported). */
 int mc_lookback_check_f32(const mc_lookback_f32 *o);
 int mc_lookback_check_f64(const mc_lookback_f64 *o);

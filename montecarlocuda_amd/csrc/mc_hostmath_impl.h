@@ -181,6 +181,101 @@ int FN(mc_barrier_closed_form)(const BARRIER *o, double *price)
     return MC_OK;
 }
 
+/* The inputs every rainbow entry point refuses (see mc_mi355x.h); with_dates: the walk's own (the closed form ignores n_dates).
+ * Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_rainbow_check)(const RAINBOW *o, int with_dates)
+{
+    const BASKET *b = &o->basket;
+    const int n = b->n;
+    if (n < 1 || n > MC_MAX_RAINBOW_ASSETS)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: n=%d outside [1, %d]", n, MC_MAX_RAINBOW_ASSETS);
+    if (!b->s || !b->v || !b->p || !b->w)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: NULL s, v, p or w");
+    if (with_dates && (o->n_dates < 1 || (long long)n * o->n_dates > MC_MAX_RAINBOW_TABLE))
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: n_dates=%d outside [1, %d / n]", o->n_dates, MC_MAX_RAINBOW_TABLE);
+    if (o->type < MC_RAINBOW_CALL_ON_MIN || o->type > MC_RAINBOW_PUT_ON_MAX)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: type=%d is none of MC_RAINBOW_CALL_ON_MIN ... MC_RAINBOW_PUT_ON_MAX", o->type);
+    if (o->barrier_type < MC_RAINBOW_NO_BARRIER || o->barrier_type > MC_BARRIER_DOWN_IN)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: barrier_type=%d is neither MC_RAINBOW_NO_BARRIER nor one of MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN",
+                                o->barrier_type);
+    const double k = (double)b->k, r = (double)b->r, t = (double)b->t;
+    if (!(t > 0) || !isfinite(t) || !isfinite(r) || !isfinite(k))
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow: need t>0 and finite k, r, t");
+    const int use_max = o->type == MC_RAINBOW_CALL_ON_MAX || o->type == MC_RAINBOW_PUT_ON_MAX;
+    double ext = 0;
+    for (int i = 0; i < n; ++i) {
+        const double s = (double)b->s[i], w = (double)b->w[i], v = (double)b->v[i];
+        if (!(s > 0) || !(w > 0) || !(v >= 0) || !isfinite(s) || !isfinite(w) || !isfinite(v))
+            return mc_internal_fail(MC_ERR_INVALID, "rainbow: need s[i]>0, w[i]>0, v[i]>=0 and finite inputs (asset %d)", i);
+        if (b->d && (double)b->d[i] != 0)
+            return mc_internal_fail(MC_ERR_INVALID, "rainbow: d[%d] is not zero: a shift of the terminal normals has no meaning on a walk", i);
+        for (int q = 0; q <= i; ++q)
+            if (!isfinite((double)b->p[i * n + q]))
+                return mc_internal_fail(MC_ERR_INVALID, "rainbow: p[%d][%d] is not finite", i, q);
+        const double level = w * s;
+        ext = i == 0 ? level : use_max ? fmax(ext, level) : fmin(ext, level);
+    }
+    if (o->barrier_type != MC_RAINBOW_NO_BARRIER) {
+        const double B = (double)o->barrier;
+        const int up = o->barrier_type <= MC_BARRIER_UP_IN;
+        if (!(B > 0) || !isfinite(B))
+            return mc_internal_fail(MC_ERR_INVALID, "rainbow: need a finite barrier > 0");
+        if (up ? ext >= B : ext <= B)
+            return mc_internal_fail(MC_ERR_INVALID, "rainbow: the initial %s level %g is on or beyond the %s barrier %g", use_max ? "best" : "worst", ext,
+                                    up ? "up" : "down", B);
+    }
+    return MC_OK;
+}
+
+/* Discounted price of the rainbow contract without a barrier at n = 1 (Black-Scholes) and n = 2 (Stulz), fp64; the formulas are
+ * stated in mc_mi355x.h. */
+int FN(mc_rainbow_closed_form)(const RAINBOW *o, double *price)
+{
+    if (!o || !price)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: NULL argument");
+    int rc = FN(mc_rainbow_check)(o, 0);
+    if (rc != MC_OK)
+        return rc;
+    const BASKET *b = &o->basket;
+    if (b->n > 2)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: n=%d, only 1 or 2 assets have one", b->n);
+    if (o->barrier_type != MC_RAINBOW_NO_BARRIER)
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: none with a barrier");
+    const double k = (double)b->k, r = (double)b->r, t = (double)b->t, st = sqrt(t), kd = k * exp(-r * t);
+    const int call = o->type <= MC_RAINBOW_CALL_ON_MAX, use_max = o->type == MC_RAINBOW_CALL_ON_MAX || o->type == MC_RAINBOW_PUT_ON_MAX;
+    if (!(k > 0))
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: needs k > 0");
+    double S[2], v[2], y[2], bs[2];
+    for (int i = 0; i < b->n; ++i) {
+        S[i] = (double)b->w[i] * (double)b->s[i], v[i] = (double)b->v[i];
+        if (!(v[i] > 0))
+            return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: needs v[%d] > 0", i);
+        y[i] = (log(S[i] / k) + (r + 0.5 * v[i] * v[i]) * t) / (v[i] * st);
+        bs[i] = S[i] * mc_norm_cdf(y[i]) - kd * mc_norm_cdf(y[i] - v[i] * st);   /* the Black-Scholes call on asset i */
+    }
+    /* the walk takes M = diag(v sqrt dt) L with L as given; the formulas price the model in which L is the factor of a CORRELATION
+     * matrix, rows of unit length (up to the rounding of an fp32 factor): any other factor is refused, not renormalised */
+    const double p00 = (double)b->p[0], p10 = b->n == 2 ? (double)b->p[2] : 0.0, p11 = b->n == 2 ? (double)b->p[3] : 1.0;
+    if (!(fabs(p00 * p00 - 1.0) <= 1e-5) || !(fabs(p10 * p10 + p11 * p11 - 1.0) <= 1e-5))
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: a row of p is not of unit length: p is not the factor of a correlation matrix");
+    if (b->n == 1) {
+        *price = call ? bs[0] : bs[0] - S[0] + kd;
+        return MC_OK;
+    }
+    const double rho = (p00 < 0 ? -p10 : p10) / sqrt(p10 * p10 + p11 * p11);   /* L_10 L_00, the rounding of the row's length taken out */
+    const double s2 = v[0] * v[0] + v[1] * v[1] - 2.0 * rho * v[0] * v[1], sg = sqrt(s2 > 0 ? s2 : 0);
+    if (!(sg * st >= 1e-8) || !(sg >= 1e-3 * (v[0] + v[1])))
+        return mc_internal_fail(MC_ERR_INVALID, "rainbow closed form: the two assets move as one (sigma=%g): price the single asset", sg);
+    const double d = (log(S[0] / S[1]) + 0.5 * s2 * t) / (sg * st);
+    const double rho1 = fmax(-1.0, fmin(1.0, (v[0] - rho * v[1]) / sg)), rho2 = fmax(-1.0, fmin(1.0, (v[1] - rho * v[0]) / sg));
+    const double cmin = S[0] * mc_binorm_cdf(y[0], -d, -rho1) + S[1] * mc_binorm_cdf(y[1], d - sg * st, -rho2) -
+                        kd * mc_binorm_cdf(y[0] - v[0] * st, y[1] - v[1] * st, rho);
+    const double margrabe = S[0] * mc_norm_cdf(d) - S[1] * mc_norm_cdf(d - sg * st);   /* PV of max(S_1 - S_2, 0) */
+    const double c = use_max ? bs[0] + bs[1] - cmin : cmin, pv = use_max ? S[1] + margrabe : S[0] - margrabe;
+    *price = call ? c : c - pv + kd;
+    return MC_OK;
+}
+
 /* The inputs every lookback entry point refuses (see mc_mi355x.h).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
 __attribute__((visibility("hidden"))) int FN(mc_lookback_check)(const LOOKBACK *o)
 {

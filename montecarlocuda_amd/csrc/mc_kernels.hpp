@@ -2179,6 +2179,192 @@ __global__ __launch_bounds__(GROUP) void barrier_kernel(const Tail /* first argu
 }
 
 // =========================================================================================
+// Worst-of / best-of ("rainbow") options on NA correlated assets walked over m equally spaced dates, with an optional barrier on
+// the same extremum, monitored on the dates (the model is stated in mc_mi355x.h).  Not in the reference.  basket_kernel's
+// host-folded Cholesky step joined to barrier_path's walk in LOG space: the lane's state is W_0 ... W_{NA-1} (one running sum of
+// normals per factor) and the running minimum of the distance to the barrier, nothing else.  Per date j
+//   cs_i = sum_{k<=i} me_ik W_k                 me = e diag(v sqrt dt) L, kernel arguments, NA (NA + 1) / 2 fmas
+//   Y    = max_i (tab_ji + cs_i)                tab_ji = e (ln(w_i s_i) + j a_i) from the per-date table (constant address space:
+//                                               scalar loads); e = -1 looks at the minimum, +1 at the maximum: both run the same code
+//   d_j  = fma(g, Y, bl)                        g = -b e, bl = b ln B; running minimum by one v_min
+// and no transcendental.  After the last date P = [min_j d_j > 0] by a select, X = E(esc Y_m) (esc = e times the exponent's unit),
+//   value = (c0 + c1 P) max(q (X - K), 0)       (c0, c1, q wave-uniform: no kernel per type; no barrier is g = bl = c1 = 0)
+//   ANTI: the same at -z (tab_ji - cs_i: the correlated sums are formed once), value = mean of the two
+// Stream: domain 14, the normal of date j (0-based here) and factor k is FLAT entry j NA + k of the Asian layout: entry % NPB of
+// block / NPB, in fp64 the pair cursor's pair entry >> 1.  The phase of a date's first entry repeats every NPB / gcd(NA, NPB) dates
+// (fp64: pairs, every 2 / gcd(NA, 2) dates): that many dates are unrolled per trip, so every entry of a trip sits at a
+// compile-time place of its block or pair, and the dates left over start a block or pair of their own.
+// =========================================================================================
+template <class Real, int NA>
+struct RainbowArgs {
+    const Real *tab;             // n_dates rows of NA values: e (ln(w_i s_i) + (j + 1) a_i), natural-log units
+    int n_dates;
+    Real me[NA * (NA + 1) / 2];  // e v_i sqrt(dt) L_ik, lower triangle by rows, natural-log units
+    Real g, bl;                  // d_j = g Y_j + bl
+    Real esc;                    // e in exponent units (natural log in f64, log2 in f32)
+    Real q, strike;
+    Real c0, c1;                 // value = (c0 + c1 P) payoff
+};
+template <class Real> using RainbowRowPtr = const __attribute__((address_space(4))) Real *;
+
+__device__ __forceinline__ double max_f64(double a, double b);   // ONE v_max_f64, defined with the lookback options below
+__device__ __forceinline__ float rainbow_max(float a, float b) { return __builtin_fmaxf(a, b); }   // pairs of them fuse into v_max3_f32
+__device__ __forceinline__ double rainbow_max(double a, double b) { return max_f64(a, b); }
+__device__ __forceinline__ float rainbow_min(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double rainbow_min(double a, double b) { return min_f64(a, b); }
+
+constexpr int rainbow_gcd(int a, int b) { return b ? rainbow_gcd(b, a % b) : a; }
+
+// Where the coefficients me live was decided per precision and size on the `make asm` listing and then on the clock (DESIGN
+// 4.14, profiles/rainbow_ab.log): kernel arguments, the scalar operand of the fmas, at every size.  fp32: no spill reload in any
+// bulk loop.  fp64: from NA = 4 M's SGPR pairs spill beside the generator's (4 ... 124 SGPRs, their v_readlane reloads in the date
+// loop) and from NA = 5 hipcc overlaps the trip's generator calls (three waves per SIMD).  A copy of M staged in LDS
+// (basket_consts_in_lds's remedy) removed every spill and 4.8's empty-asm tie between the generator calls gave four waves at
+// NA = 3 ... 6 -- and both were SLOWER: LDS 4 to 9 % at NA = 3 ... 7 (level at NA = 8: 1.4 % faster, inside the spread, and only in
+// a form that spilled to scratch), the tie 2 to 4 % (12 % at NA = 8), both together 3 to 10 %.  The walk is bound by the vector pipe: overlapped generator calls are worth more to it than a fourth wave,
+// and a v_readlane costs less than a ds_read and its wait.  Asking for four waves (amdgpu_waves_per_eu) at NA = 7, 8 spills vector
+// registers to scratch.  None of the three is in the code.
+
+// one date: the extremum of the NA log levels from the factors' running sums, and the running minimum of the distance
+template <bool ANTI, class Real, int NA>
+__device__ __forceinline__ void rainbow_date(const RainbowArgs<Real, NA> &o, RainbowRowPtr<Real> row, const Real (&W)[NA], Real &Y, Real &Y_m,
+                                             Real &mn, Real &mn_m)
+{
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        Real cs = o.me[i * (i + 1) / 2] * W[0];
+#pragma unroll
+        for (int k = 1; k <= i; ++k)
+            cs = fma_r(o.me[i * (i + 1) / 2 + k], W[k], cs);
+        const Real t = row[i];
+        Y = i ? rainbow_max(Y, t + cs) : t + cs;
+        if (ANTI)
+            Y_m = i ? rainbow_max(Y_m, t - cs) : t - cs;
+    }
+    mn = rainbow_min(mn, fma_r(o.g, Y, o.bl));
+    if (ANTI)
+        mn_m = rainbow_min(mn_m, fma_r(o.g, Y_m, o.bl));
+}
+
+template <class Real, int NA>
+__device__ __forceinline__ Real rainbow_value(Real mn, Real Y, const RainbowArgs<Real, NA> &o)
+{
+    const Real P = mn > 0 ? (Real)1 : (Real)0;
+    const Real pay = o.q * (exp_model(o.esc * Y) - o.strike);
+    return fma_r(o.c1, P, o.c0) * (pay > 0 ? pay : 0);
+}
+
+// fp32: blocks of four normals; NPB / gcd(NA, NPB) = 4, 2 or 1 dates per trip for NA odd, = 2 mod 4, = 0 mod 4
+template <bool ANTI, int NA, class Gen>
+__device__ __forceinline__ float rainbow_path(Gen &gen, const RainbowArgs<float, NA> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    constexpr int U = NPB / rainbow_gcd(NA, NPB), BPT = U * NA / NPB;   // dates and blocks per trip
+    const int n = o.n_dates;
+    const RainbowRowPtr<float> tab = (RainbowRowPtr<float>)o.tab;
+    float W[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+        W[k] = 0;
+    float Y = 0, Y_m = 0, mn = __builtin_inff(), mn_m = __builtin_inff();
+    float z[NPB];
+    // date d of the trip that starts at date j and block blk: entries d NA ... d NA + NA - 1 of the trip, places known at compile time
+    auto date = [&](int d, int j, uint32_t blk) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const int e = d * NA + k;
+            if (e % NPB == 0)
+                gen.normals(w, c0, blk + (uint32_t)(e / NPB), 14u /*MC_DOMAIN_RAINBOW*/, z);
+            W[k] += z[e % NPB];
+        }
+        rainbow_date<ANTI>(o, tab + (j + d) * NA, W, Y, Y_m, mn, mn_m);
+    };
+    int j = 0;
+    uint32_t blk = 0;
+#pragma unroll 1
+    for (; j + U <= n; j += U, blk += BPT) {
+#pragma unroll
+        for (int d = 0; d < U; ++d)
+            date(d, j, blk);
+    }
+#pragma unroll
+    for (int d = 0; d < U - 1; ++d)   // wave-uniform: up to U - 1 dates left, the first at the start of a block
+        if (j + d < n)
+            date(d, j, blk);
+    float val = rainbow_value(mn, Y, o);
+    if (ANTI)
+        val = 0.5f * (val + rainbow_value(mn_m, Y_m, o));
+    return val;
+}
+
+// fp64: Box-Muller pairs through the generator's pair cursor, drawn strictly in order; two dates per trip for odd NA (its second
+// date starts on the second normal of a pair), one for even NA.  The cursor's four-phase state is resolved by a scalar branch per
+// pair (asian_path<double>'s remainder loop).  A bulk loop of 8 / gcd(NA, 8) dates with compile-time phases was built and dropped
+// on the listing: it cost vector registers at NA = 1, 2 (92 -> 99 and 126, four waves for five), gained none at NA = 3, 5, 7 and
+// doubled the code; with the tie and the LDS copy it took 121 registers for 100 at NA = 4 and three waves at NA = 6.
+template <bool ANTI, int NA, class Gen>
+__device__ __forceinline__ double rainbow_path(Gen &gen, const RainbowArgs<double, NA> &o, const Work &w, uint32_t c0)
+{
+    constexpr int U = 2 / rainbow_gcd(NA, 2), PPT = U * NA / 2;   // dates and pairs per trip
+    const int n = o.n_dates;
+    const RainbowRowPtr<double> tab = (RainbowRowPtr<double>)o.tab;
+    double W[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+        W[k] = 0;
+    double Y = 0, Y_m = 0, mn = __builtin_inf(), mn_m = __builtin_inf();
+    double zp[2];
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    auto date = [&](int d, int j, uint32_t pr) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const int e = d * NA + k;
+            if (e % 2 == 0)
+                gen.pair(w, c0, 14u /*MC_DOMAIN_RAINBOW*/, pr + (uint32_t)(e / 2), carry, zp[0], zp[1]);
+            W[k] += zp[e % 2];
+        }
+        rainbow_date<ANTI>(o, tab + (j + d) * NA, W, Y, Y_m, mn, mn_m);
+    };
+    int j = 0;
+    uint32_t pr = 0;
+#pragma unroll 1
+    for (; j + U <= n; j += U, pr += PPT) {
+#pragma unroll
+        for (int d = 0; d < U; ++d)
+            date(d, j, pr);
+    }
+    if (U > 1 && j < n)   // wave-uniform: odd NA and an odd number of dates; the last pair's second normal is not used
+        date(0, j, pr);
+    gen.pairs_done((uint32_t)((n * NA + 1) >> 1));
+    double val = rainbow_value(mn, Y, o);
+    if (ANTI)
+        val = 0.5 * (val + rainbow_value(mn_m, Y_m, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths: barrier_kernel's frame
+template <class Real, int NA, bool ANTI, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void rainbow_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const RainbowArgs<Real, NA> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = rainbow_path<ANTI, NA>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // Lookback options on m equally spaced dates: the payoff is written on the running maximum or minimum of the spot, taken on
 // the dates (CONT = false) or continuously, by sampling the maximum of the Brownian bridge between them (CONT = true).  Not in
 // the reference.  barrier_path's walk in LOG space: the lane's state is W_j and the running maximum of the signed excursion

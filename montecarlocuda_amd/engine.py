@@ -96,6 +96,28 @@ class _BasketHolder:
         self.struct = _lib.BASKET[X](self.n, *[a.ctypes.data_as(P) for a in self.arrs], b.k, b.t, b.r)
 
 
+class _RainbowHolder(_BasketHolder):
+    """mc_rainbow_*: a basket (MultiOptionData or dict; "d" may be left out of a dict: zeros) with the contract's fields, or a dict
+    that carries "n_dates" and optionally "kind", "barrier", "barrier_kind" itself.  kind: a name of _lib.RAINBOW_TYPES or the
+    header's integer; barrier_kind: a name of _lib.BARRIER_TYPES, its integer, or None with barrier=None for no barrier."""
+
+    def __init__(self, X, b, n_dates=None, kind=None, barrier=None, barrier_kind=None):
+        if isinstance(b, dict):
+            if n_dates is None:
+                n_dates, kind = b["n_dates"], b.get("kind", "put-on-min")
+                barrier, barrier_kind = b.get("barrier"), b.get("barrier_kind")
+            b = dict(b, d=b.get("d", np.zeros(len(b["s"]))))
+        super().__init__(X, b)
+        if (barrier is None) != (barrier_kind is None):
+            raise ValueError("rainbow: barrier and barrier_kind go together")
+        kind = _lib.RAINBOW_TYPES[kind] if isinstance(kind, str) else int(kind)
+        if barrier_kind is None:
+            barrier, barrier_kind = 0.0, _lib.RAINBOW_NO_BARRIER
+        barrier_kind = _lib.BARRIER_TYPES[barrier_kind] if isinstance(barrier_kind, str) else int(barrier_kind)
+        self.basket = self.struct
+        self.struct = _lib.RAINBOW[X](self.basket, float(barrier), int(n_dates), kind, barrier_kind)
+
+
 def _as_cva(X, c) -> C.Structure:
     if isinstance(c, dict):
         c = CVA(c["defint"], c["lgd"], OptionData(*(c[k] for k in "skrvt")), c["n_grid"])
@@ -440,6 +462,15 @@ class Engine:
         the dates: unbiased for the continuously monitored price, barrier_closed_form).  Honours set_antithetic."""
         return self._run("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
 
+    def rainbow(self, basket, n_dates, n_paths, kind="put-on-min", barrier=None, barrier_kind=None, seed=MC_DEFAULT_SEED, first_path=0,
+                precision="f64") -> Estimate:
+        """Worst-of / best-of option on the basket's correlated assets walked over n_dates dates (mc_rainbow_run_*): kind is
+        "call-on-min", "call-on-max", "put-on-min" or "put-on-max"; barrier and barrier_kind ("up-and-out" ... "down-and-in") put a
+        barrier on the same extremum, monitored on the dates.  The basket's k, t, r are the strike, maturity and rate.  Honours
+        set_antithetic."""
+        h = _RainbowHolder(precision, basket, n_dates, kind, barrier, barrier_kind)
+        return self._run("rainbow", precision, h.struct, seed, first_path, n_paths)
+
     def lookback(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
                  monitoring="discrete") -> Estimate:
         """Lookback option on n_dates equally spaced dates (mc_lookback_run_*).  kind: "floating-call", "floating-put", "fixed-call",
@@ -542,6 +573,9 @@ class Engine:
             return h, h
         if prod == "merton":   # inputs: the option's fields plus "lambda", "mu_j", "delta", "n_dates" and optionally "payoff", "barrier", "kind"
             return _as_merton(precision, inputs), None
+        if prod == "rainbow":   # inputs: the basket's fields ("d" optional) plus "n_dates" and optionally "kind", "barrier", "barrier_kind"
+            h = _RainbowHolder(precision, inputs)
+            return h.struct, h
         if prod == "lookback":   # inputs: the option's fields plus "n_dates" and optionally "kind", "monitoring"
             return _as_lookback(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
@@ -571,6 +605,11 @@ class Engine:
     def barrier_paths(self, opt, barrier, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="up-and-out",
                       monitoring="discrete"):
         return self._paths("barrier", precision, _as_barrier(precision, opt, barrier, n_dates, kind, monitoring), seed, first_path, n_paths)
+
+    def rainbow_paths(self, basket, n_dates, n_paths, kind="put-on-min", barrier=None, barrier_kind=None, seed=MC_DEFAULT_SEED, first_path=0,
+                      precision="f64"):
+        h = _RainbowHolder(precision, basket, n_dates, kind, barrier, barrier_kind)
+        return self._paths("rainbow", precision, h.struct, seed, first_path, n_paths)
 
     def lookback_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
                        monitoring="discrete"):
@@ -718,6 +757,15 @@ def barrier_closed_form(opt, barrier, kind="up-and-out", precision="f64"):
     """Discounted Reiner-Rubinstein price of the continuously monitored single-barrier call (no dividend, no rebate; fp64)."""
     p = C.c_double()
     check(getattr(lib(), f"mc_barrier_closed_form_{precision}")(C.byref(_as_barrier(precision, opt, barrier, 1, kind, "continuous")), C.byref(p)))
+    return p.value
+
+
+def rainbow_closed_form(basket, kind="put-on-min", barrier=None, barrier_kind=None, precision="f64"):
+    """Discounted price of the worst-of / best-of option without a barrier on one asset (Black-Scholes) or two (Stulz); fp64, plain
+    C, no GPU.  Refuses more assets and a barrier."""
+    p = C.c_double()
+    h = _RainbowHolder(precision, basket, 1, kind, barrier, barrier_kind)
+    check(getattr(lib(), f"mc_rainbow_closed_form_{precision}")(C.byref(h.struct), C.byref(p)))
     return p.value
 
 
