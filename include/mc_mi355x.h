@@ -78,6 +78,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_AMERICAN 12u /* the pricing pass of the Bermudan options, see mc_american_run_* */
 #define MC_DOMAIN_AMERICAN_FIT 13u /* the fit of their exercise rule, see mc_american_fit_*: never the paths the rule is priced on */
 #define MC_DOMAIN_RAINBOW 14u /* worst-of / best-of options on a correlated basket walked over dates, see mc_rainbow_run_* */
+#define MC_DOMAIN_AUTOCALL 15u /* worst-of autocallable notes on the same walk, see mc_autocall_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -189,6 +190,18 @@ enum { MC_RAINBOW_CALL_ON_MIN = 0, MC_RAINBOW_CALL_ON_MAX = 1, MC_RAINBOW_PUT_ON
 enum { MC_RAINBOW_NO_BARRIER = -1 };
 typedef struct { mc_basket_f32 basket; float barrier; int n_dates, type, barrier_type; } mc_rainbow_f32;
 typedef struct { mc_basket_f64 basket; double barrier; int n_dates, type, barrier_type; } mc_rainbow_f64;
+
+/* Worst-of autocallable ("Phoenix") note on basket.n correlated assets, 1 <= n <= MC_MAX_RAINBOW_ASSETS, walked over n_dates
+ * equally spaced dates of which n_obs are observation dates (see mc_autocall_run_*).  Not in the reference.  The basket is read
+ * exactly as mc_rainbow_run_* reads it; basket.k is the strike of the put on the worst level.  autocall and coupon_barrier are
+ * arrays of n_obs levels, copied during the call: no pointer is retained.  The table holds n values per date and three per
+ * observation, read through scalar loads: the cap keeps it the size of the scalar data cache, as MC_MAX_RAINBOW_TABLE does. */
+#define MC_MAX_AUTOCALL_TABLE 4096   /* n * n_dates + 3 * n_obs at most */
+enum { MC_AUTOCALL_KI_NONE = -1, MC_AUTOCALL_KI_DATES = 0, MC_AUTOCALL_KI_MATURITY = 1 };
+typedef struct { mc_basket_f32 basket; const float *autocall; const float *coupon_barrier; float coupon, barrier, gearing;
+                 int n_dates, n_obs, memory, ki_monitoring; } mc_autocall_f32;
+typedef struct { mc_basket_f64 basket; const double *autocall; const double *coupon_barrier; double coupon, barrier, gearing;
+                 int n_dates, n_obs, memory, ki_monitoring; } mc_autocall_f64;
 
 /* ---- outputs ------------------------------------------------------------------------ */
 typedef struct {
@@ -736,8 +749,7 @@ int mc_american_lattice_f64(const mc_american_f64 *opt, int steps_per_date, doub
  * barrier, barrier <= 0 or the initial extremum of w_i s_i not strictly on the live side of it (up: >= barrier, down: <=
  * barrier); a nonzero basket.d; the control variate switched on (there is none); the range errors of the other products.
  * MC_ERR_UNSUPPORTED: a XORWOW context, MC_NORMALS_F32 on the _f64 calls, a context set up for external normals or the launch
- * geometry.  The context stays usable.  Not offered: continuous monitoring, unequal dates, per-asset barriers, autocall and
- * coupon schedules, Asian and lookback payoffs on the basket, Greeks, n > 8. */
+ * geometry.  The context stays usable.  Not offered: continuous monitoring, unequal dates, per-asset barriers, Asian and lookback payoffs on the basket, Greeks, n > 8. */
 int mc_rainbow_run_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
 int mc_rainbow_run_f64(mc_context *ctx, const mc_rainbow_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
 int mc_rainbow_launch_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
@@ -748,6 +760,52 @@ int mc_rainbow_paths_f32(mc_context *ctx, const mc_rainbow_f32 *opt, uint64_t se
 int mc_rainbow_paths_f64(mc_context *ctx, const mc_rainbow_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 int mc_rainbow_closed_form_f32(const mc_rainbow_f32 *opt, double *price);
 int mc_rainbow_closed_form_f64(const mc_rainbow_f64 *opt, double *price);
+
+/* ---- worst-of autocallable notes: memory coupons, early redemption, a knock-in put ---------------
+ * The model of mc_rainbow_run_* with the extremum fixed to the minimum: n assets, n_dates equally spaced dates t_j = j t / n_dates,
+ *   y(j) = min_i y_i(j) = ln min_i (w_i S_i(t_j))          y_i(j), a_i, M, W_k(j) as stated there; w_i = 1/s_i: performance levels
+ * n_obs observation dates, n_dates % n_obs == 0, E = n_dates / n_obs: observation k = 1 ... n_obs falls on date k E.
+ *   autocall[k-1] = A_k > 0         the trigger level; INFINITY: not callable at this observation
+ *   coupon_barrier[k-1] = C_k >= 0  0: the coupon is unconditional
+ *   coupon = c >= 0                 the amount per observation, notional 1;  memory = 0 / 1
+ *   barrier = B > 0                 the knock-in level;  ki_monitoring: MC_AUTOCALL_KI_DATES (all walk dates 1 ... n_dates),
+ *                                   MC_AUTOCALL_KI_MATURITY (date n_dates only) or MC_AUTOCALL_KI_NONE (the put is always
+ *                                   live, barrier is ignored)
+ *   gearing = g >= 0                the standard note is g = 1 / basket.k;  g = 0: no put
+ * Per path direction, with alive = 1, miss = 0, V = 0, at observation k on date j = k E, in this order:
+ *   called = [y(j) >= ln A_k]                  equality counts as reached
+ *   paid   = [y(j) >= ln min(A_k, C_k)]        a called note always pays its coupon
+ *   cash   = paid ? fma(c memory, miss, c) : 0,  then  miss = paid ? 0 : miss + 1
+ *   k < n_obs:  V = fma(alive D_k, cash + called, V),  then  alive = called ? 0 : alive
+ *   k = n_obs:  V = fma(alive D_k, fma(-(KI ? g : 0), max(basket.k - exp(y(n_dates)), 0), cash + 1), V)
+ *   D_k = exp(-r t k / n_obs), the discount factor of date k E, folded on the host in fp64 and rounded once, as ln A_k and
+ *   ln min(A_k, C_k) are (+-infinity allowed: every decision compares the log level with the table value itself)
+ *   KI = 1 for MC_AUTOCALL_KI_NONE; otherwise KI = [min over the monitored dates of y(j) <= ln B]: a touch counts, t_0 is not
+ *   monitored
+ *   antithetic: the mean of V at z and at -z
+ * V is a PRESENT VALUE: every flow carries its own discount factor.  mc_autocall_run_* fills expected with mean(V);
+ * mc_autocall_launch_* is the asynchronous form (device triple, then mc_closing with the discount 1; several GPUs:
+ * mc_shard_range per device).  mc_autocall_paths_* returns V itself (n_paths <= 2^26): unlike the other mc_*_paths_* calls,
+ * whose per-path values are undiscounted, these are discounted.
+ *
+ * Stream: path p is unit p of MC_DOMAIN_AUTOCALL; the rainbow's flat layout unchanged: the normal of date j (1-based) and factor
+ * k (0-based) is flat entry (j - 1) n + k.  A path that is called draws no normals it does not need: the values do not depend on it.
+ *
+ * MC_ERR_INVALID before anything is enqueued: everything mc_rainbow_run_* refuses about the basket and the ranges; n_obs < 1 or
+ * n_dates % n_obs != 0; n n_dates + 3 n_obs > MC_MAX_AUTOCALL_TABLE; a NULL array; A_k <= 0 or NaN; C_k < 0, NaN or infinite;
+ * coupon < 0, gearing < 0, basket.k <= 0; ki_monitoring out of range; memory not 0 / 1; with a knock-in, barrier <= 0 or the initial
+ * worst level <= barrier; the control variate switched on (there is none).  MC_ERR_UNSUPPORTED: as for mc_rainbow_run_* (a
+ * XORWOW context, MC_NORMALS_F32 on the _f64 calls, external normals, the launch geometry).  The context stays usable.
+ * Not offered: per-asset barriers, continuous knock-in monitoring, unequal observation dates, per-observation coupon amounts, an
+ * exact single-asset price, Greeks, a control variate, a book, n > 8. */
+int mc_autocall_run_f32(mc_context *ctx, const mc_autocall_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_autocall_run_f64(mc_context *ctx, const mc_autocall_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_autocall_launch_f32(mc_context *ctx, const mc_autocall_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_autocall_launch_f64(mc_context *ctx, const mc_autocall_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_autocall_paths_f32(mc_context *ctx, const mc_autocall_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_autocall_paths_f64(mc_context *ctx, const mc_autocall_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
 
 /* ---- a book of vanilla calls in one launch ----------------------------------------------------
  * Entry i prices option i on its own seed and path range [first_path, first_path + n_paths); out[i] / triple i is that

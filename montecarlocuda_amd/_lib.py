@@ -35,6 +35,9 @@ MAX_RAINBOW_ASSETS = 8   # MC_MAX_RAINBOW_ASSETS
 MAX_RAINBOW_TABLE = 4096   # MC_MAX_RAINBOW_TABLE: n * n_dates at most
 RAINBOW_TYPES = {"call-on-min": 0, "call-on-max": 1, "put-on-min": 2, "put-on-max": 3}   # MC_RAINBOW_CALL_ON_MIN ... MC_RAINBOW_PUT_ON_MAX
 RAINBOW_NO_BARRIER = -1   # MC_RAINBOW_NO_BARRIER
+DOMAIN_AUTOCALL = 15   # the worst-of autocallable notes: the rainbow's flat layout
+MAX_AUTOCALL_TABLE = 4096   # MC_MAX_AUTOCALL_TABLE: n * n_dates + 3 * n_obs at most
+AUTOCALL_KI = {None: -1, "dates": 0, "maturity": 1}   # MC_AUTOCALL_KI_NONE, MC_AUTOCALL_KI_DATES, MC_AUTOCALL_KI_MATURITY
 BARRIER_TYPES = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}   # MC_BARRIER_UP_OUT ... MC_BARRIER_DOWN_IN
 LOOKBACK_TYPES = {"floating-call": 0, "floating-put": 1, "fixed-call": 2, "fixed-put": 3}   # MC_LOOKBACK_FLOAT_CALL ... MC_LOOKBACK_FIXED_PUT
 MONITORING = {"discrete": 0, "continuous": 1}   # MC_MONITOR_DISCRETE, MC_MONITOR_CONTINUOUS
@@ -146,6 +149,18 @@ class RainbowF64(C.Structure):   # mc_rainbow_f64
     _fields_ = [("basket", BasketF64), ("barrier", C.c_double), ("n_dates", C.c_int), ("type", C.c_int), ("barrier_type", C.c_int)]
 
 
+def _autocall(B, R):
+    P = C.POINTER(R)
+
+    class Autocall(C.Structure):   # mc_autocall_f32 / mc_autocall_f64
+        _fields_ = [("basket", B), ("autocall", P), ("coupon_barrier", P), ("coupon", R), ("barrier", R), ("gearing", R),
+                    ("n_dates", C.c_int), ("n_obs", C.c_int), ("memory", C.c_int), ("ki_monitoring", C.c_int)]
+    return Autocall
+
+
+AutocallF32, AutocallF64 = _autocall(BasketF32, C.c_float), _autocall(BasketF64, C.c_double)
+
+
 class Result(C.Structure):
     _fields_ = [("expected", C.c_double), ("confidence", C.c_double), ("sum", C.c_double), ("sum2", C.c_double),
                 ("n", C.c_uint64), ("kernel_ms", C.c_float), ("wall_ms", C.c_float)]
@@ -189,6 +204,7 @@ MERTON = {"f32": MertonF32, "f64": MertonF64}
 AMERICAN = {"f32": AmericanF32, "f64": AmericanF64}
 HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 RAINBOW = {"f32": RainbowF32, "f64": RainbowF64}
+AUTOCALL = {"f32": AutocallF32, "f64": AutocallF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
@@ -213,6 +229,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
     EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
     EXPORTS += [f"mc_rainbow_run_{_x}", f"mc_rainbow_launch_{_x}", f"mc_rainbow_paths_{_x}", f"mc_rainbow_closed_form_{_x}"]
+    EXPORTS += [f"mc_autocall_run_{_x}", f"mc_autocall_launch_{_x}", f"mc_autocall_paths_{_x}"]
     EXPORTS += [f"mc_merton_run_{_x}", f"mc_merton_launch_{_x}", f"mc_merton_paths_{_x}", f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}"]
     EXPORTS += [f"mc_american_run_{_x}", f"mc_american_launch_{_x}", f"mc_american_paths_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
     TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
@@ -308,6 +325,9 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_rainbow_run_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_rainbow_paths_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, RP]
         getattr(L, f"mc_rainbow_closed_form_{X}").argtypes = [C.POINTER(RAINBOW[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_autocall_launch_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
+        getattr(L, f"mc_autocall_run_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, C.POINTER(Result)]
+        getattr(L, f"mc_autocall_paths_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, RP]
         getattr(L, f"mc_merton_launch_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
         getattr(L, f"mc_merton_run_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.POINTER(Result)]
         getattr(L, f"mc_merton_paths_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, RP]

@@ -85,7 +85,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a rainbow option's per-date rows, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a rainbow option's per-date rows, an autocallable note's per-date and per-observation rows, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
     void *fit_state = nullptr;    // a Longstaff-Schwartz fit's per-path state (W, V), its device table and the fp64 copy of beta: grown on demand
     size_t fit_state_bytes = 0;
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
@@ -2412,6 +2412,140 @@ static int rainbow_enqueue(mc_context *c, const typename RainbowIn<Real>::type *
 }
 
 // ---------------------------------------------------------------------------------------
+// Worst-of autocallable notes on the rainbow's walk: autocall_kernel, one lane per path
+// ---------------------------------------------------------------------------------------
+template <class Real> struct AutocallIn;
+template <> struct AutocallIn<float> { using type = mc_autocall_f32; using rainbow = mc_rainbow_f32; };
+template <> struct AutocallIn<double> { using type = mc_autocall_f64; using rainbow = mc_rainbow_f64; };
+
+// Everything the header lists under MC_ERR_INVALID.  The basket, the ranges and the knock-in level are checked by the rainbow's
+// own check on the worst-of down-and-in put of the same basket, dates and barrier (its messages say "rainbow"); the schedule here.
+template <class Real>
+static int autocall_check(const typename AutocallIn<Real>::type &v)
+{
+    if (v.ki_monitoring < MC_AUTOCALL_KI_NONE || v.ki_monitoring > MC_AUTOCALL_KI_MATURITY)
+        return fail(MC_ERR_INVALID, "autocall: ki_monitoring=%d is none of MC_AUTOCALL_KI_NONE, MC_AUTOCALL_KI_DATES, MC_AUTOCALL_KI_MATURITY", v.ki_monitoring);
+    typename AutocallIn<Real>::rainbow w{v.basket, v.barrier, v.n_dates, MC_RAINBOW_PUT_ON_MIN,
+                                         v.ki_monitoring == MC_AUTOCALL_KI_NONE ? MC_RAINBOW_NO_BARRIER : MC_BARRIER_DOWN_IN};
+    if (int rc = rainbow_check(w)) return rc;
+    const int n = v.basket.n;
+    if (v.n_obs < 1 || v.n_dates % v.n_obs != 0)
+        return fail(MC_ERR_INVALID, "autocall: n_obs=%d must be at least 1 and divide n_dates=%d", v.n_obs, v.n_dates);
+    if ((long long)n * v.n_dates + 3ll * v.n_obs > MC_MAX_AUTOCALL_TABLE)
+        return fail(MC_ERR_INVALID, "autocall: n n_dates + 3 n_obs = %lld values, more than %d", (long long)n * v.n_dates + 3ll * v.n_obs, MC_MAX_AUTOCALL_TABLE);
+    if (!v.autocall || !v.coupon_barrier)
+        return fail(MC_ERR_INVALID, "autocall: NULL autocall or coupon_barrier");
+    for (int k = 0; k < v.n_obs; ++k) {
+        const double A = (double)v.autocall[k], C = (double)v.coupon_barrier[k];
+        if (!(A > 0))
+            return fail(MC_ERR_INVALID, "autocall: need autocall[%d] > 0 (INFINITY: not callable)", k);
+        if (!(C >= 0) || !std::isfinite(C))
+            return fail(MC_ERR_INVALID, "autocall: need a finite coupon_barrier[%d] >= 0", k);
+    }
+    if (!(v.coupon >= 0) || !std::isfinite((double)v.coupon) || !(v.gearing >= 0) || !std::isfinite((double)v.gearing))
+        return fail(MC_ERR_INVALID, "autocall: need finite coupon >= 0 and gearing >= 0");
+    if (!(v.basket.k > 0))
+        return fail(MC_ERR_INVALID, "autocall: need the put strike basket.k > 0");
+    if (v.memory != 0 && v.memory != 1)
+        return fail(MC_ERR_INVALID, "autocall: memory=%d is neither 0 nor 1", v.memory);
+    return MC_OK;
+}
+
+// The constants folded in fp64 and rounded once, and the table in the context's buffer: the per-date rows ln(w_i s_i) + j a_i,
+// j = 1 ... n_dates, then per observation k = 1 ... n_obs the three values ln A_k, ln min(A_k, C_k), D_k = exp(-r t k / n_obs).
+// The arrays are read here and nowhere later.
+template <class Real, int NA>
+static int autocall_table_ready(mc_context *c, const typename AutocallIn<Real>::type *v, hipStream_t st, AutocallArgs<Real, NA> &args)
+{
+    const auto &o = v->basket;
+    const double m = (double)v->n_dates, dt = (double)o.t / m, sdt = std::sqrt(dt);
+    const bool has_ki = v->ki_monitoring != MC_AUTOCALL_KI_NONE;
+    const double ln_b = has_ki ? std::log((double)v->barrier) : 0.0;
+    static thread_local std::vector<Real> tab;
+    tab.resize((size_t)v->n_dates * NA + 3 * (size_t)v->n_obs);
+    for (int i = 0; i < NA; ++i) {
+        const double vi = (double)o.v[i], a = ((double)o.r - 0.5 * vi * vi) * dt, ln_s = std::log((double)o.w[i] * (double)o.s[i]);
+        double row = 0;
+        for (int k = 0; k <= i; ++k) {
+            const double mik = vi * sdt * (double)o.p[i * NA + k];
+            args.me[i * (i + 1) / 2 + k] = (Real)mik;
+            row += std::fabs(mik);
+        }
+        if (!(std::fabs(ln_s) + std::fabs(ln_b) + m * (std::fabs(a) + row * Z_MAX_F64) < EXP_F64_ARG_LIMIT))
+            return fail(MC_ERR_INVALID, "autocall: drift and volatility put the simulated level of asset %d outside the range of a double", i);
+        for (int j = 1; j <= v->n_dates; ++j)
+            tab[(size_t)(j - 1) * NA + i] = (Real)(ln_s + (double)j * a);
+    }
+    Real *obs = tab.data() + (size_t)v->n_dates * NA;
+    for (int k = 1; k <= v->n_obs; ++k, obs += 3) {
+        const double A = (double)v->autocall[k - 1], C = (double)v->coupon_barrier[k - 1];
+        obs[0] = (Real)std::log(A);                  // +inf: not callable
+        obs[1] = (Real)std::log(std::fmin(A, C));    // -inf: the coupon is unconditional
+        obs[2] = (Real)std::exp(-(double)o.r * ((double)o.t * (double)k / (double)v->n_obs));
+    }
+    if (int rc = c->table.upload(c, st, table_key(tab, 'U'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    args.tab = (const Real *)c->table.d;
+    args.n_dates = v->n_dates;
+    args.n_obs = v->n_obs;
+    args.every = v->n_dates / v->n_obs;
+    args.ki_dates = v->ki_monitoring == MC_AUTOCALL_KI_DATES;
+    args.lb = has_ki ? (Real)ln_b : std::numeric_limits<Real>::infinity();
+    args.esc = (Real)exp_scale<Real>();
+    args.strike = o.k;
+    args.g = v->gearing;
+    args.c = v->coupon;
+    args.cm = v->memory ? v->coupon : (Real)0;
+    return MC_OK;
+}
+
+template <class Real, int NA>
+static int autocall_enqueue_n(mc_context *c, const typename AutocallIn<Real>::type *v, uint64_t seed, uint64_t n, double *d_triple, hipStream_t st,
+                              Real *out, const std::vector<Segment> &segs)
+{
+    AutocallArgs<Real, NA> args;
+    if (int rc = autocall_table_ready<Real, NA>(c, v, st, args)) return rc;
+    ProfileScope prof(c);
+    return launch_call(
+        c, st, 1.0, 1.0, n, d_triple, segs, {}, [&](const Segment &s, int) { return grid_for(c->blocks, s.count, GRID_SCALE_CVA); },
+        [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
+            const Work w = context_work(c, seed, s, 0, 0);
+            Real *dst = out ? out + done : (Real *)nullptr;
+            if (c->antithetic) launch_sim(prof, autocall_kernel<Real, NA, true>, g, st, t, args, w, dst);
+            else               launch_sim(prof, autocall_kernel<Real, NA, false>, g, st, t, args, w, dst);
+            return MC_OK;
+        });
+}
+
+template <class Real>
+static int autocall_enqueue(mc_context *c, const typename AutocallIn<Real>::type *v, uint64_t seed, uint64_t first, uint64_t n,
+                            double *d_triple, hipStream_t st, Real *out)
+{
+    // refusals first: nothing is enqueued, no table is touched
+    if (c->ext)
+        return fail(MC_ERR_UNSUPPORTED, "autocall: no external-normals or launch-geometry form");
+    if (c->rng == MC_RNG_XORWOW)
+        return fail(MC_ERR_UNSUPPORTED, "autocall: Philox only (XORWOW is one sequence per lane: another sample definition)");
+    if (sizeof(Real) == 8 && c->normals_f32)
+        return fail(MC_ERR_UNSUPPORTED, "autocall: fp32 normals in the fp64 kernels are not implemented for this product");
+    if (c->control)
+        return fail(MC_ERR_INVALID, "autocall: no control variate");
+    if (int rc = autocall_check<Real>(*v)) return rc;
+    std::vector<Segment> segs;
+    if (int rc = plan_segments(first, n, segs)) return rc;
+    if (int rc = begin_call(c, st)) return rc;
+    switch (v->basket.n) {
+    case 1: return autocall_enqueue_n<Real, 1>(c, v, seed, n, d_triple, st, out, segs);
+    case 2: return autocall_enqueue_n<Real, 2>(c, v, seed, n, d_triple, st, out, segs);
+    case 3: return autocall_enqueue_n<Real, 3>(c, v, seed, n, d_triple, st, out, segs);
+    case 4: return autocall_enqueue_n<Real, 4>(c, v, seed, n, d_triple, st, out, segs);
+    case 5: return autocall_enqueue_n<Real, 5>(c, v, seed, n, d_triple, st, out, segs);
+    case 6: return autocall_enqueue_n<Real, 6>(c, v, seed, n, d_triple, st, out, segs);
+    case 7: return autocall_enqueue_n<Real, 7>(c, v, seed, n, d_triple, st, out, segs);
+    default: return autocall_enqueue_n<Real, 8>(c, v, seed, n, d_triple, st, out, segs);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Lookback options, discrete or Brownian-bridge continuous extrema: lookback_kernel, one lane per path
 // ---------------------------------------------------------------------------------------
 template <class Real> struct LookbackIn;
@@ -3870,6 +4004,30 @@ static int grid_cva(mc_context *c, const typename CvaIn<Real>::type *o, int nb, 
         if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
         return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
             return rainbow_enqueue<Real>(c, o, seed, first, n, t, st, d);                                    \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_autocall_launch_##X(mc_context *c, const mc_autocall_##X *o, uint64_t seed, uint64_t first,\
+                                          uint64_t n, double *d_triple, void *stream)                        \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, d_triple)) return rc;                                      \
+        ArmScope arm(c);                                                                                     \
+        return autocall_enqueue<Real>(c, o, seed, first, n, d_triple, pick_stream(c, stream), nullptr);      \
+    }                                                                                                        \
+    extern "C" int mc_autocall_run_##X(mc_context *c, const mc_autocall_##X *o, uint64_t seed, uint64_t first,\
+                                       uint64_t n, mc_result *out)                                           \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, out)) return rc;                                           \
+        /* the per-path value is a present value already: every flow carries its own discount factor */      \
+        return run_sync(c, n, 1.0, out, [&](hipStream_t st, double *t) {                                     \
+            return autocall_enqueue<Real>(c, o, seed, first, n, t, st, nullptr);                             \
+        });                                                                                                  \
+    }                                                                                                        \
+    extern "C" int mc_autocall_paths_##X(mc_context *c, const mc_autocall_##X *o, uint64_t seed, uint64_t first,\
+                                         uint64_t n, Real *h_out)                                            \
+    {                                                                                                        \
+        if (int rc = check_common(c, o, first, n, h_out)) return rc;                                         \
+        return dump_sync<Real>(c, n, h_out, [&](hipStream_t st, double *t, Real *d) {                        \
+            return autocall_enqueue<Real>(c, o, seed, first, n, t, st, d);                                   \
         });                                                                                                  \
     }                                                                                                        \
     extern "C" int mc_lookback_launch_##X(mc_context *c, const mc_lookback_##X *o, uint64_t seed, uint64_t first,\

@@ -2365,6 +2365,243 @@ __global__ __launch_bounds__(GROUP) void rainbow_kernel(const Tail /* first argu
 }
 
 // =========================================================================================
+// Worst-of autocallable notes on NA correlated assets: memory coupons, early redemption on observation dates and a knock-in put at
+// maturity (the model is stated in mc_mi355x.h).  Not in the reference.  rainbow_path's walk with the extremum fixed to the
+// minimum, in the same trips of compile-time phases, but the path PAYS ON THE WAY and may end before the last date.  Per date j
+//   y = min_i (tab_ji + cs_i),  mn = min(mn, y)         tab_ji = ln(w_i s_i) + j a_i, cs_i as in the rainbow's step (me = +M)
+// and, where date j is the next observation (a wave-uniform compare of two integers, one scalar branch), for observation k < n_obs
+//   called = [y >= LA_k],  paid = [y >= LP_k]            LA_k = ln A_k, LP_k = ln min(A_k, C_k): +-inf allowed, compared directly
+//   cash = paid ? fma(cm, miss, c) : 0                   cm = c memory;  miss = paid ? 0 : miss + 1
+//   V = fma(alive D_k, cash + called, V)                 D_k = exp(-r t_kE), folded on the host;  alive = called ? 0 : alive
+// (LA_k, LP_k, D_k: three values per observation behind the per-date rows of the same table, scalar loads).  After the last date
+//   KI = [(ki_dates ? mn : y) <= lb]                     lb = ln B, +inf without a knock-in condition
+//   V = fma(alive D, fma(-(KI ? g : 0), max(K - E(esc y), 0), cash + 1), V)
+// so the date loop holds no transcendental, every decision is a compare of the log level against a table value, and alive, miss
+// and V move by selects and fmas.  ANTI: the same at -z, value = mean of the two.
+// Early exit (MC_AUTOCALL_EARLY_EXIT, compiled OUT): after an observation a wave none of whose lanes is alive in either direction
+// can leave the date loop; what it skips would be multiplied by alive = 0, so no value changes.  The stream is counter-based
+// (GenPhilox: every block and pair is addressed by its index, the pair cursor's carry is refilled at pair 0 of the next path and
+// pairs_done does nothing), so drawing fewer entries than n NA needs no bookkeeping; the generators that keep a sequence are refused
+// by the host.  Built and timed against the kernel without it (tools/autocall_speed.py, profiles/autocall_ab.log): a
+// wave leaves only when all of its 64 paths are called, which a traded note's schedule never brings about (a third of its paths
+// reach maturity), so the exit bought nothing on it and cost its ballot per observation; it stays a switch of the build.
+// Stream: domain 15, the rainbow's flat (date, factor) layout.
+// =========================================================================================
+#ifndef MC_AUTOCALL_EARLY_EXIT
+#define MC_AUTOCALL_EARLY_EXIT 0   // decided on the clock: DESIGN 4.15, profiles/autocall_ab.log
+#endif
+
+template <class Real, int NA>
+struct AutocallArgs {
+    const Real *tab;             // n_dates rows of NA values ln(w_i s_i) + (j + 1) a_i, then n_obs rows (LA_k, LP_k, D_k)
+    int n_dates, n_obs, every;   // every = n_dates / n_obs walk dates per observation
+    int ki_dates;                // the knock-in looks at the minimum over all dates (1) or at the level at maturity (0)
+    Real me[NA * (NA + 1) / 2];  // v_i sqrt(dt) L_ik, lower triangle by rows, natural-log units
+    Real lb;                     // ln B; +inf: the put is always live
+    Real esc;                    // the exponent's unit (natural log in f64, log2 in f32)
+    Real strike, g;
+    Real c, cm;                  // the coupon, and the coupon times the memory switch
+};
+
+// what one path direction carries between the dates
+template <class Real>
+struct AutocallSide {
+    Real y, mn, alive, miss, V;
+};
+
+// one date: the minimum of the NA log levels from the factors' running sums, and its running minimum (rainbow_date's step)
+template <bool ANTI, class Real, int NA>
+__device__ __forceinline__ void autocall_date(const AutocallArgs<Real, NA> &o, RainbowRowPtr<Real> row, const Real (&W)[NA], AutocallSide<Real> &p,
+                                              AutocallSide<Real> &q)
+{
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        Real cs = o.me[i * (i + 1) / 2] * W[0];
+#pragma unroll
+        for (int k = 1; k <= i; ++k)
+            cs = fma_r(o.me[i * (i + 1) / 2 + k], W[k], cs);
+        const Real t = row[i];
+        p.y = i ? rainbow_min(p.y, t + cs) : t + cs;
+        if (ANTI)
+            q.y = i ? rainbow_min(q.y, t - cs) : t - cs;
+    }
+    p.mn = rainbow_min(p.mn, p.y);
+    if (ANTI)
+        q.mn = rainbow_min(q.mn, q.y);
+}
+
+template <class Real, int NA>
+__device__ __forceinline__ Real autocall_cash(const AutocallArgs<Real, NA> &o, Real LP, AutocallSide<Real> &p)
+{
+    const bool paid = p.y >= LP;
+    const Real cash = paid ? fma_r(o.cm, p.miss, o.c) : (Real)0;
+    p.miss = paid ? (Real)0 : p.miss + (Real)1;
+    return cash;
+}
+
+// an observation before the last: the coupon, and the redemption of a path that is called
+template <class Real, int NA>
+__device__ __forceinline__ void autocall_observe(const AutocallArgs<Real, NA> &o, RainbowRowPtr<Real> obs, AutocallSide<Real> &p)
+{
+    const Real LA = obs[0], LP = obs[1], D = obs[2];
+    const bool called = p.y >= LA;
+    const Real cash = autocall_cash(o, LP, p);
+    p.V = fma_r(p.alive * D, cash + (called ? (Real)1 : (Real)0), p.V);
+    p.alive = called ? (Real)0 : p.alive;
+}
+
+// the last observation: the coupon, the notional and the knock-in put
+template <class Real, int NA>
+__device__ __forceinline__ Real autocall_maturity(const AutocallArgs<Real, NA> &o, RainbowRowPtr<Real> obs, AutocallSide<Real> &p)
+{
+    const Real LP = obs[1], D = obs[2];
+    const Real cash = autocall_cash(o, LP, p);
+    const Real gk = (o.ki_dates ? p.mn : p.y) <= o.lb ? o.g : (Real)0;
+    const Real put = o.strike - exp_model(o.esc * p.y);
+    return fma_r(p.alive * D, fma_r(-gk, put > 0 ? put : (Real)0, cash + (Real)1), p.V);
+}
+
+template <bool ANTI, class Real>
+__device__ __forceinline__ bool autocall_wave_dead(const AutocallSide<Real> &p, const AutocallSide<Real> &q)
+{
+    return __builtin_amdgcn_ballot_w64(p.alive != 0 || (ANTI && q.alive != 0)) == 0;
+}
+
+template <class Real>
+__device__ __forceinline__ AutocallSide<Real> autocall_start()
+{
+    return AutocallSide<Real>{(Real)0, (Real)__builtin_inf(), (Real)1, (Real)0, (Real)0};
+}
+
+// fp32: blocks of four normals, rainbow_path's trips
+template <bool ANTI, int NA, class Gen>
+__device__ __forceinline__ float autocall_path(Gen &gen, const AutocallArgs<float, NA> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    constexpr int U = NPB / rainbow_gcd(NA, NPB), BPT = U * NA / NPB;   // dates and blocks per trip
+    const int n = o.n_dates;
+    const RainbowRowPtr<float> tab = (RainbowRowPtr<float>)o.tab, obs = tab + n * NA;
+    float W[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+        W[k] = 0;
+    AutocallSide<float> p = autocall_start<float>(), q = autocall_start<float>();
+    float z[NPB];
+    int next = o.every, k_obs = 0;   // the date (1-based) of the next observation, and its row
+    bool dead = false;               // wave-uniform
+    auto date = [&](int d, int j, uint32_t blk) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const int e = d * NA + k;
+            if (e % NPB == 0)
+                gen.normals(w, c0, blk + (uint32_t)(e / NPB), 15u /*MC_DOMAIN_AUTOCALL*/, z);
+            W[k] += z[e % NPB];
+        }
+        autocall_date<ANTI>(o, tab + (j + d) * NA, W, p, q);
+        if (j + d + 1 == next && next != n) {   // wave-uniform: the last observation is taken after the loop
+            autocall_observe(o, obs + 3 * k_obs, p);
+            if (ANTI)
+                autocall_observe(o, obs + 3 * k_obs, q);
+            next += o.every, ++k_obs;
+            if (MC_AUTOCALL_EARLY_EXIT)
+                dead = autocall_wave_dead<ANTI>(p, q);
+        }
+    };
+    int j = 0;
+    uint32_t blk = 0;
+#pragma unroll 1
+    for (; j + U <= n && !dead; j += U, blk += BPT) {
+#pragma unroll
+        for (int d = 0; d < U; ++d)
+            date(d, j, blk);
+    }
+    if (!dead) {
+#pragma unroll
+        for (int d = 0; d < U - 1; ++d)   // wave-uniform: up to U - 1 dates left, the first at the start of a block
+            if (j + d < n)
+                date(d, j, blk);
+    }
+    float val = autocall_maturity(o, obs + 3 * (o.n_obs - 1), p);
+    if (ANTI)
+        val = 0.5f * (val + autocall_maturity(o, obs + 3 * (o.n_obs - 1), q));
+    return val;
+}
+
+// fp64: the generator's pair cursor, rainbow_path's trips.  A wave that leaves early has drawn fewer pairs than pairs_done is
+// told: the counter-based generators this product is served with ignore the count.
+template <bool ANTI, int NA, class Gen>
+__device__ __forceinline__ double autocall_path(Gen &gen, const AutocallArgs<double, NA> &o, const Work &w, uint32_t c0)
+{
+    constexpr int U = 2 / rainbow_gcd(NA, 2), PPT = U * NA / 2;   // dates and pairs per trip
+    const int n = o.n_dates;
+    const RainbowRowPtr<double> tab = (RainbowRowPtr<double>)o.tab, obs = tab + n * NA;
+    double W[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+        W[k] = 0;
+    AutocallSide<double> p = autocall_start<double>(), q = autocall_start<double>();
+    double zp[2];
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    int next = o.every, k_obs = 0;
+    bool dead = false;
+    auto date = [&](int d, int j, uint32_t pr) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const int e = d * NA + k;
+            if (e % 2 == 0)
+                gen.pair(w, c0, 15u /*MC_DOMAIN_AUTOCALL*/, pr + (uint32_t)(e / 2), carry, zp[0], zp[1]);
+            W[k] += zp[e % 2];
+        }
+        autocall_date<ANTI>(o, tab + (j + d) * NA, W, p, q);
+        if (j + d + 1 == next && next != n) {
+            autocall_observe(o, obs + 3 * k_obs, p);
+            if (ANTI)
+                autocall_observe(o, obs + 3 * k_obs, q);
+            next += o.every, ++k_obs;
+            if (MC_AUTOCALL_EARLY_EXIT)
+                dead = autocall_wave_dead<ANTI>(p, q);
+        }
+    };
+    int j = 0;
+    uint32_t pr = 0;
+#pragma unroll 1
+    for (; j + U <= n && !dead; j += U, pr += PPT) {
+#pragma unroll
+        for (int d = 0; d < U; ++d)
+            date(d, j, pr);
+    }
+    if (U > 1 && j < n && !dead)   // wave-uniform: odd NA and an odd number of dates; the last pair's second normal is not used
+        date(0, j, pr);
+    gen.pairs_done((uint32_t)((n * NA + 1) >> 1));
+    double val = autocall_maturity(o, obs + 3 * (o.n_obs - 1), p);
+    if (ANTI)
+        val = 0.5 * (val + autocall_maturity(o, obs + 3 * (o.n_obs - 1), q));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths: rainbow_kernel's frame and reduction
+template <class Real, int NA, bool ANTI, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void autocall_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const AutocallArgs<Real, NA> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = autocall_path<ANTI, NA>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // Lookback options on m equally spaced dates: the payoff is written on the running maximum or minimum of the spot, taken on
 // the dates (CONT = false) or continuously, by sampling the maximum of the Brownian bridge between them (CONT = true).  Not in
 // the reference.  barrier_path's walk in LOG space: the lane's state is W_j and the running maximum of the signed excursion

@@ -118,6 +118,46 @@ class _RainbowHolder(_BasketHolder):
         self.struct = _lib.RAINBOW[X](self.basket, float(barrier), int(n_dates), kind, barrier_kind)
 
 
+class _AutocallHolder(_BasketHolder):
+    """mc_autocall_*: a basket (MultiOptionData or dict; "d" may be left out of a dict: zeros) with the note's fields, or a dict that
+    carries "n_dates", "autocall", "coupon_barrier", "coupon" and optionally "barrier", "ki", "gearing", "memory", "n_obs" itself.
+    autocall and coupon_barrier: a sequence of n_obs levels each, or a scalar with an explicit n_obs."""
+
+    def __init__(self, X, b, n_dates=None, autocall=None, coupon_barrier=None, coupon=None, barrier=None, ki="dates", gearing=None, memory=True,
+                 n_obs=None):
+        if isinstance(b, dict):
+            if n_dates is None:
+                n_dates, autocall, coupon_barrier, coupon = b["n_dates"], b["autocall"], b["coupon_barrier"], b["coupon"]
+                barrier, ki, gearing = b.get("barrier"), b.get("ki", "dates"), b.get("gearing")
+                memory, n_obs = b.get("memory", True), b.get("n_obs")
+            b = dict(b, d=b.get("d", np.zeros(len(b["s"]))))
+        super().__init__(X, b)
+        levels = []
+        for name, a in (("autocall", autocall), ("coupon_barrier", coupon_barrier)):
+            if np.ndim(a) == 0:
+                if n_obs is None:
+                    raise ValueError(f"autocall: a scalar {name} needs an explicit n_obs")
+                a = np.full(max(int(n_obs), 0), a)
+            a = np.ascontiguousarray(a, dtype=NP[X]).reshape(-1)
+            n_obs = a.size if n_obs is None else int(n_obs)
+            if a.size != max(n_obs, 0):
+                raise ValueError(f"autocall: {name} has {a.size} levels for n_obs={n_obs}")
+            levels.append(a)
+        if ki not in _lib.AUTOCALL_KI:
+            ki_code = int(ki)
+        else:
+            ki_code = _lib.AUTOCALL_KI[ki]
+        if (barrier is None) != (ki_code == _lib.AUTOCALL_KI[None]):
+            raise ValueError("autocall: a knock-in level goes with ki=\"dates\" or \"maturity\", none with ki=None")
+        if gearing is None:
+            gearing = 1.0 / self.struct.k if self.struct.k > 0 else 0.0   # k <= 0 is refused by the library
+        self.levels = levels
+        self.basket = self.struct
+        P = C.POINTER(_lib.CT[X])
+        self.struct = _lib.AUTOCALL[X](self.basket, levels[0].ctypes.data_as(P), levels[1].ctypes.data_as(P), float(coupon),
+                                       0.0 if barrier is None else float(barrier), float(gearing), int(n_dates), n_obs, int(memory), ki_code)
+
+
 def _as_cva(X, c) -> C.Structure:
     if isinstance(c, dict):
         c = CVA(c["defint"], c["lgd"], OptionData(*(c[k] for k in "skrvt")), c["n_grid"])
@@ -471,6 +511,18 @@ class Engine:
         h = _RainbowHolder(precision, basket, n_dates, kind, barrier, barrier_kind)
         return self._run("rainbow", precision, h.struct, seed, first_path, n_paths)
 
+    def autocall(self, basket, n_dates, n_paths, autocall, coupon_barrier, coupon, barrier=None, ki="dates", gearing=None, memory=True,
+                 seed=MC_DEFAULT_SEED, first_path=0, precision="f64", n_obs=None) -> Estimate:
+        """Worst-of autocallable note on the basket's correlated assets walked over n_dates dates (mc_autocall_run_*).  autocall and
+        coupon_barrier: the trigger and coupon levels per observation date, a sequence of n_obs values each (n_obs must divide
+        n_dates) or a scalar with an explicit n_obs=; math.inf as a trigger: not callable there; 0 as a coupon level: unconditional.
+        coupon: the amount per observation (notional 1), memory: missed coupons are paid with the next one.  barrier: the knock-in
+        level of the put struck at the basket's k, monitored on all dates (ki="dates") or at maturity only (ki="maturity");
+        ki=None with barrier=None: the put is always live.  gearing=None: 1 / k.  `expected` is the note's present value.  Honours
+        set_antithetic."""
+        h = _AutocallHolder(precision, basket, n_dates, autocall, coupon_barrier, coupon, barrier, ki, gearing, memory, n_obs)
+        return self._run("autocall", precision, h.struct, seed, first_path, n_paths)
+
     def lookback(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
                  monitoring="discrete") -> Estimate:
         """Lookback option on n_dates equally spaced dates (mc_lookback_run_*).  kind: "floating-call", "floating-put", "fixed-call",
@@ -576,6 +628,9 @@ class Engine:
         if prod == "rainbow":   # inputs: the basket's fields ("d" optional) plus "n_dates" and optionally "kind", "barrier", "barrier_kind"
             h = _RainbowHolder(precision, inputs)
             return h.struct, h
+        if prod == "autocall":   # inputs: the basket's fields ("d" optional) plus "n_dates", "autocall", "coupon_barrier", "coupon" and optionally "barrier", "ki", "gearing", "memory", "n_obs"
+            h = _AutocallHolder(precision, inputs)
+            return h.struct, h
         if prod == "lookback":   # inputs: the option's fields plus "n_dates" and optionally "kind", "monitoring"
             return _as_lookback(precision, inputs), None
         if prod == "barrier":   # inputs: the option's fields plus "barrier", "n_dates" and optionally "kind", "monitoring"
@@ -610,6 +665,12 @@ class Engine:
                       precision="f64"):
         h = _RainbowHolder(precision, basket, n_dates, kind, barrier, barrier_kind)
         return self._paths("rainbow", precision, h.struct, seed, first_path, n_paths)
+
+    def autocall_paths(self, basket, n_dates, n_paths, autocall, coupon_barrier, coupon, barrier=None, ki="dates", gearing=None, memory=True,
+                       seed=MC_DEFAULT_SEED, first_path=0, precision="f64", n_obs=None):
+        """The per-path present values of autocall() (discounted, unlike the other *_paths)."""
+        h = _AutocallHolder(precision, basket, n_dates, autocall, coupon_barrier, coupon, barrier, ki, gearing, memory, n_obs)
+        return self._paths("autocall", precision, h.struct, seed, first_path, n_paths)
 
     def lookback_paths(self, opt, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64", kind="floating-call",
                        monitoring="discrete"):
