@@ -7,6 +7,7 @@
  *   - the simulation kernels on a caller-supplied normal stream (mc_*_from_normals_*): how the reference's own glibc
  *     normal stream is pushed through the HIP hot kernels and compared with numbers the compiled reference printed;
  *   - generator dumps: Philox/XORWOW normals and words (mc_normals_*, mc_words, mc_xorwow_words, mc_grid_normals);
+ *   - the device's fp64 elementary functions and words-to-normals steps on caller-chosen inputs (mc_math_probe);
  *   - the launch-geometry mode's two forms side by side: mc_context_set_grid_form, per-path dumps mc_*_paths_grid_*.
  */
 #ifndef MC_MI355X_TEST_H_
@@ -40,6 +41,26 @@ int mc_words(mc_context *ctx, uint64_t seed, uint32_t domain, uint64_t first_uni
 
 /* The first `count` normals of every thread's stream: h_out[(b * num_threads + t) * count + k] (tests). */
 int mc_grid_normals(mc_context *ctx, int num_blocks, int num_threads, uint32_t count, float *h_out);
+
+/* ---- the device's math on caller-chosen inputs ---------------------------------------------------------------------------
+ * The shipping inline functions of csrc/mc_math_f64.hpp and the words-to-normals plumbing of csrc/mc_rng.hpp, evaluated by
+ * one probe kernel (256-lane workgroups, LDS tables staged as every fp64 kernel stages them) on the inputs of the HOST
+ * array h_in; item i runs on lane i mod 256.  An item is MC_PROBE_IN 64-bit words of input and MC_PROBE_OUT of output; doubles
+ * travel as their bit patterns, 32-bit words and floats (as their bit patterns) zero-extended.  n <= 2^20.
+ *   op                  in[]                     out[]
+ *   MC_PROBE_NEG2LOG    u                        neg2log_unit_tab(u), the same on F64K
+ *   MC_PROBE_SINCOS     lo, hi                   sin, cos of sincos_turns_tab(lo, hi), sin, cos on F64K
+ *   MC_PROBE_EXP        x                        exp_f64(x)
+ *   MC_PROBE_SQRT       x                        sqrt_pos(x)
+ *   MC_PROBE_RECIP      a1, a2, b1, b2           recip_pos(a1); recip2_pos(a1, a2): 1/a1, 1/a2; recip4_pos: 1/a1, 1/a2, 1/b1, 1/b2
+ *   MC_PROBE_U01        lo, hi                   u01_f64(lo, hi)
+ *   MC_PROBE_PAIR       a, m, c                  z_cos, z_sin of pair_normals_f64(a, m, c), z_cos, z_sin on F64K
+ *   MC_PROBE_F32_BLOCK  x, y, z, w               the four floats of words_to_normals, u01_f32(x), angle_f32(y), u01_f32(z), angle_f32(w) */
+enum { MC_PROBE_NEG2LOG = 0, MC_PROBE_SINCOS = 1, MC_PROBE_EXP = 2, MC_PROBE_SQRT = 3, MC_PROBE_RECIP = 4, MC_PROBE_U01 = 5,
+       MC_PROBE_PAIR = 6, MC_PROBE_F32_BLOCK = 7, MC_PROBE_OPS = 8 };
+#define MC_PROBE_IN 4
+#define MC_PROBE_OUT 8
+int mc_math_probe(mc_context *ctx, int op, const uint64_t *h_in, uint64_t n, uint64_t *h_out);
 
 
 /* ---- test hooks: the simulation kernels on a caller-supplied normal stream -------------------------------------

@@ -216,7 +216,10 @@ EXPORTS = ["mc_last_error", "mc_device_count", "mc_device_pci_bus_id", "mc_conte
            "mc_context_set_normals", "mc_context_set_cva_date_lanes", "mc_basket_control_mean_f32", "mc_basket_control_mean_f64", "mc_closing", "mc_shard_range",
            "mc_chol_f32", "mc_chol_f64", "mc_factor_from_cov_f32", "mc_factor_from_cov_f64"]
 EXPORTS.append("mc_american_solve")
-TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_set_grid_form"]
+TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_set_grid_form", "mc_math_probe"]
+# mc_math_probe (include/mc_mi355x_test.h): operations, and 64-bit words per item in and out
+PROBE_OPS = {"neg2log": 0, "sincos": 1, "exp": 2, "sqrt": 3, "recip": 4, "u01": 5, "pair": 6, "f32_block": 7}
+PROBE_IN, PROBE_OUT, PROBE_MAX = 4, 8, 1 << 20
 for _x in ("f32", "f64"):
     for _p in ("vanilla", "basket", "cva"):
         EXPORTS += [f"mc_{_p}_launch_{_x}", f"mc_{_p}_run_{_x}", f"mc_{_p}_paths_{_x}"]
@@ -274,6 +277,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.mc_context_set_grid_form.argtypes = [ctx, C.c_int]
     L.mc_words.argtypes = [ctx, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.mc_xorwow_words.argtypes = [ctx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.mc_math_probe.argtypes = [ctx, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
     L.mc_american_solve.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     for X in ("f32", "f64"):
         getattr(L, f"mc_basket_control_mean_{X}").argtypes = [C.POINTER(BASKET[X]), C.POINTER(C.c_double)]

@@ -4209,6 +4209,23 @@ extern "C" int mc_words(mc_context *c, uint64_t seed, uint32_t domain, uint64_t 
         return MC_OK;
     });
 }
+
+// The device's math on caller-chosen inputs (test hook, mc_mi355x_test.h): math_probe_kernel, item i on lane i mod 256
+static_assert(PROBE_IN == MC_PROBE_IN && PROBE_OUT == MC_PROBE_OUT, "the probe's item layout is the header's");
+extern "C" int mc_math_probe(mc_context *c, int op, const uint64_t *h_in, uint64_t n, uint64_t *h_out)
+{
+    if (int rc = check_common(c, h_in, 0, n, h_out)) return rc;
+    if (op < 0 || op >= MC_PROBE_OPS || n > (1ull << 20))
+        return fail(MC_ERR_INVALID, "mc_math_probe: unknown operation, or more than 2^20 items");
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_ext(c, n * PROBE_IN * sizeof(uint64_t))) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_ext, h_in, n * PROBE_IN * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    return dump_sync<uint64_t>(c, n * PROBE_OUT, h_out, [&](hipStream_t st, double *, uint64_t *d) -> int {
+        math_probe_kernel<<<grid_for(c->blocks, n), GROUP, 0, st>>>(op, (uint32_t)n, (const uint64_t *)c->d_ext, d);
+        HIPCHK(hipGetLastError());
+        return MC_OK;
+    });
+}
 MC_DEFINE_FROM_NORMALS(f32, float)
 MC_DEFINE_GRID(f32, float)
 MC_DEFINE_FROM_NORMALS(f64, double)

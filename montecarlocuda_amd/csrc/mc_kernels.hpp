@@ -4362,6 +4362,84 @@ __global__ __launch_bounds__(GROUP) void normals_kernel(const Work w, uint32_t b
     }
 }
 
+// =========================================================================================
+// Math probe (test hook mc_math_probe, include/mc_mi355x_test.h): the inline functions of mc_math_f64.hpp and the words-to-normals
+// steps of mc_rng.hpp -- the functions themselves, as every kernel above calls them -- on caller-chosen inputs.  Item i (PROBE_IN
+// 64-bit words in, PROBE_OUT out; doubles as bit patterns, 32-bit values zero-extended) runs on lane i mod 256, so neighbouring
+// lanes read different table rows.  `op` is wave-uniform: the numbers are the MC_PROBE_* of the header.
+// =========================================================================================
+constexpr int PROBE_IN = 4, PROBE_OUT = 8;
+__global__ __launch_bounds__(GROUP) void math_probe_kernel(int op, uint32_t n, const uint64_t *__restrict__ in, uint64_t *__restrict__ out)
+{
+    stage_f64_tables();
+    F64K K;
+    K.load();
+    const auto dbl = [](uint64_t b) { return __longlong_as_double((long long)b); };
+    const auto bits = [](double d) { return (uint64_t)__double_as_longlong(d); };
+    const auto fbits = [](float f) { return (uint64_t)__float_as_uint(f); };
+    const uint32_t stride = gridDim.x * GROUP;
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < n; i += stride) {
+        const uint64_t *x = in + (uint64_t)i * PROBE_IN;
+        uint64_t *y = out + (uint64_t)i * PROBE_OUT;
+        uint64_t r[PROBE_OUT] = {0, 0, 0, 0, 0, 0, 0, 0};
+        switch (op) {
+        case 0:   // MC_PROBE_NEG2LOG
+            r[0] = bits(neg2log_unit_tab(dbl(x[0])));
+            r[1] = bits(neg2log_unit_tab(dbl(x[0]), K));
+            break;
+        case 1: {   // MC_PROBE_SINCOS
+            double s, c;
+            sincos_turns_tab((uint32_t)x[0], (uint32_t)x[1], s, c);
+            r[0] = bits(s), r[1] = bits(c);
+            sincos_turns_tab((uint32_t)x[0], (uint32_t)x[1], K, s, c);
+            r[2] = bits(s), r[3] = bits(c);
+            break;
+        }
+        case 2:   // MC_PROBE_EXP
+            r[0] = bits(exp_f64(dbl(x[0])));
+            break;
+        case 3:   // MC_PROBE_SQRT
+            r[0] = bits(sqrt_pos(dbl(x[0])));
+            break;
+        case 4: {   // MC_PROBE_RECIP
+            const double a1 = dbl(x[0]), a2 = dbl(x[1]), b1 = dbl(x[2]), b2 = dbl(x[3]);
+            double q[6];
+            r[0] = bits(recip_pos(a1));
+            recip2_pos(a1, a2, q[0], q[1]);
+            recip4_pos(a1, a2, b1, b2, q[2], q[3], q[4], q[5]);
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                r[1 + j] = bits(q[j]);
+            break;
+        }
+        case 5:   // MC_PROBE_U01
+            r[0] = bits(u01_f64((uint32_t)x[0], (uint32_t)x[1]));
+            break;
+        case 6: {   // MC_PROBE_PAIR
+            double zc, zs;
+            pair_normals_f64((uint32_t)x[0], (uint32_t)x[1], (uint32_t)x[2], zc, zs);
+            r[0] = bits(zc), r[1] = bits(zs);
+            pair_normals_f64((uint32_t)x[0], (uint32_t)x[1], (uint32_t)x[2], K, zc, zs);
+            r[2] = bits(zc), r[3] = bits(zs);
+            break;
+        }
+        default: {   // MC_PROBE_F32_BLOCK
+            const u32x4 w = {(uint32_t)x[0], (uint32_t)x[1], (uint32_t)x[2], (uint32_t)x[3]};
+            float z[4];
+            words_to_normals(w, z);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                r[j] = fbits(z[j]);
+            r[4] = fbits(u01_f32(w.x)), r[5] = fbits(angle_f32(w.y)), r[6] = fbits(u01_f32(w.z)), r[7] = fbits(angle_f32(w.w));
+            break;
+        }
+        }
+#pragma unroll
+        for (int j = 0; j < PROBE_OUT; ++j)
+            y[j] = r[j];
+    }
+}
+
 // Raw words dump (the tests rebuild the bridge uniforms from them): Philox blocks first_block .. first_block + n_blocks - 1 of
 // each unit, four words per block, unit-major: out[(i * n_blocks + b) * 4 + k].
 __global__ __launch_bounds__(GROUP) void words_kernel(const Work w, uint32_t domain, uint32_t first_block, uint32_t n_blocks, uint32_t *__restrict__ out)

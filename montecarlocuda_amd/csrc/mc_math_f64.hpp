@@ -18,6 +18,8 @@
 //                                          2-/3-term series on |b| <= 2 pi / 512
 // tools/check_f64_tables.c (host twin, vs 80-bit libm over 4e7 inputs): -2 ln u within 2.8e-16 relative,
 // sin/cos within 1.7e-16 absolute, the normal within 1.8e-15 absolute, exp within 1.09 ulp.
+// The functions themselves on the device, at the edges of their domains -- including sqrt_pos and recip*_pos, which no CPU can restate:
+// tests/test_gpu_math_edges.py through the probe kernel (mc_kernels.hpp: math_probe_kernel); figures in profiles/math_edges.log.
 //
 // History of the variants that lost their in-process A/B runs (polynomial-only log 37 / sincos 36 / exp 19 instructions,
 // ocml exp, coefficients in constant memory, two v_rcp_f64 instead of one shared, a second sqrt residual step, the
@@ -124,6 +126,8 @@ __device__ __forceinline__ double sqrt_pos(double x)
 // from the high word); slot i = top 7 bits of the shifted mantissa;
 // r' = m c2_i + 2 = -2 (m c_i - 1), |r'| <= 2^-7;  -2 ln m = t_i + r' + r'^2/4 + r'^3/12 + ... + r'^7/448.
 // The slot that contains m = 1 has c = 1, t = 0, so u -> 1 keeps its relative accuracy.
+// (From below, which is where the generators' uniforms live.  Above that slot, u in (1.00015, sqrt 2), t_i + S cancel towards u -> 1
+// and only the absolute error stays small: 2.3e-15 relative at u = 1.00015 -- tests/math_ref.py: check_neg2log.  No kernel passes u > 1.)
 __device__ __forceinline__ double neg2log_unit_tab(double u)
 {
     const int h = __double2hiint(u) - 0x3fe6a09e;

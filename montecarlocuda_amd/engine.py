@@ -718,6 +718,20 @@ class Engine:
         check(lib().mc_words(self._ctx, seed, domain, first_unit, n_units, first_block, n_blocks, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
+    def math_probe(self, op, inputs):
+        """The device's own math on caller-chosen inputs (test hook, mc_math_probe): `op` is a key of _lib.PROBE_OPS, `inputs` an
+        (n, k <= 4) array of uint64 (doubles as bit patterns, 32-bit words zero-extended); item i runs on lane i mod 256.
+        Returns (n, 8) uint64 in the layout include/mc_mi355x_test.h lists."""
+        x = np.asarray(inputs, dtype=np.uint64)
+        x = x.reshape(len(x), -1)
+        n = len(x)
+        buf = np.zeros((n, _lib.PROBE_IN), dtype=np.uint64)
+        buf[:, :x.shape[1]] = x
+        out = np.empty((n, _lib.PROBE_OUT), dtype=np.uint64)
+        P = C.POINTER(C.c_uint64)
+        check(lib().mc_math_probe(self._ctx, _lib.PROBE_OPS[op], buf.ctypes.data_as(P), n, out.ctypes.data_as(P)))
+        return out
+
     # ---- compatibility mode: the reference's launch geometry and per-thread XORWOW streams (mc_*_run_grid_*) ----
     def run_grid(self, prod, inputs, num_blocks, num_threads, paths_per_block, precision="f64") -> Estimate:
         """num_blocks * paths_per_block paths drawn the reference's way (dp/MonteCarloKernel.cu:285-290: one XORWOW state per

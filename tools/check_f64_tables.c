@@ -1,6 +1,8 @@
 /* Host check of the table-driven fp64 Box-Muller pieces (same arithmetic as mc_math_f64.hpp, written with
  * C99 fma): max error against 80-bit long double libm over random and edge inputs.
- *   gcc -O2 -ffp-contract=off -o /tmp/check_f64_tables tools/check_f64_tables.c -lm && /tmp/check_f64_tables */
+ *   gcc -O2 -ffp-contract=off -o /tmp/check_f64_tables tools/check_f64_tables.c -lm && /tmp/check_f64_tables
+ * With -DCHECK_F64_TABLES_LIB -shared -fPIC the twin's functions are exported (twin_*) and main is left out: tests/test_math_ref.py
+ * evaluates them on the edge lists of tests/math_ref.py. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -71,6 +73,12 @@ static double exp_tab(double x)
     return ldexp(fma(T, r * p, T), ni >> 8);
 }
 
+#ifdef CHECK_F64_TABLES_LIB
+double twin_u01(uint32_t lo, uint32_t hi) { return u01(lo, hi); }
+double twin_neg2log(double u) { return neg2log_unit_tab(u); }
+void twin_sincos(uint32_t lo, uint32_t hi, double *s, double *c) { sincos_turns_tab(lo, hi, s, c); }
+double twin_exp(double x) { return exp_tab(x); }
+#else
 static uint64_t st = 88172645463325252ull;
 static uint64_t rnd(void) { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; }
 
@@ -114,3 +122,4 @@ int main(int argc, char **argv)
     printf("normal  : max absolute error %.3e\n", max_z);
     return !(max_rel < 4e-16 && max_abs_sc < 2e-16 && max_exp < 3e-16 && max_z < 4e-15);
 }
+#endif
