@@ -206,6 +206,10 @@ HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 RAINBOW = {"f32": RainbowF32, "f64": RainbowF64}
 AUTOCALL = {"f32": AutocallF32, "f64": AutocallF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
+# every product has the entry points mc_<product>_launch_*, _run_* and _paths_* over its input struct; the Bermudan ones also take
+# the exercise rule, a const double *, behind the struct
+PRODUCTS = {"vanilla": OPTION, "basket": BASKET, "cva": CVA, "asian": ASIAN, "barrier": BARRIER, "lookback": LOOKBACK, "rainbow": RAINBOW,
+            "autocall": AUTOCALL, "merton": MERTON, "american": AMERICAN, "heston": HESTON, "heston_path": HESTON_PATH}
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -221,23 +225,17 @@ TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_se
 PROBE_OPS = {"neg2log": 0, "sincos": 1, "exp": 2, "sqrt": 3, "recip": 4, "u01": 5, "pair": 6, "f32_block": 7}
 PROBE_IN, PROBE_OUT, PROBE_MAX = 4, 8, 1 << 20
 for _x in ("f32", "f64"):
-    for _p in ("vanilla", "basket", "cva"):
+    for _p in PRODUCTS:
         EXPORTS += [f"mc_{_p}_launch_{_x}", f"mc_{_p}_run_{_x}", f"mc_{_p}_paths_{_x}"]
     EXPORTS += [f"mc_{_p}_run_grid_{_x}" for _p in ("vanilla", "basket", "cva")]       # the reference's launch geometry
     EXPORTS += [f"mc_vanilla_greeks_run_{_x}", f"mc_vanilla_greeks_lr_run_{_x}", f"mc_basket_greeks_run_{_x}", f"mc_cva_greeks_run_{_x}",
                 f"mc_basket_greeks_lr_run_{_x}", f"mc_cva_greeks_lr_run_{_x}"]
     EXPORTS += [f"mc_vanilla_greeks2_run_{_x}", f"mc_basket_gamma_run_{_x}"]
     EXPORTS += [f"mc_vanilla_book_run_{_x}", f"mc_vanilla_book_launch_{_x}"]
-    EXPORTS += [f"mc_asian_run_{_x}", f"mc_asian_launch_{_x}", f"mc_asian_paths_{_x}", f"mc_asian_control_mean_{_x}"]
-    EXPORTS += [f"mc_barrier_run_{_x}", f"mc_barrier_launch_{_x}", f"mc_barrier_paths_{_x}", f"mc_barrier_closed_form_{_x}"]
-    EXPORTS += [f"mc_lookback_run_{_x}", f"mc_lookback_launch_{_x}", f"mc_lookback_paths_{_x}", f"mc_lookback_closed_form_{_x}"]
-    EXPORTS += [f"mc_rainbow_run_{_x}", f"mc_rainbow_launch_{_x}", f"mc_rainbow_paths_{_x}", f"mc_rainbow_closed_form_{_x}"]
-    EXPORTS += [f"mc_autocall_run_{_x}", f"mc_autocall_launch_{_x}", f"mc_autocall_paths_{_x}"]
-    EXPORTS += [f"mc_merton_run_{_x}", f"mc_merton_launch_{_x}", f"mc_merton_paths_{_x}", f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}"]
-    EXPORTS += [f"mc_american_run_{_x}", f"mc_american_launch_{_x}", f"mc_american_paths_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
+    EXPORTS += [f"mc_asian_control_mean_{_x}", f"mc_barrier_closed_form_{_x}", f"mc_lookback_closed_form_{_x}", f"mc_rainbow_closed_form_{_x}"]
+    EXPORTS += [f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
+    EXPORTS.append(f"mc_heston_closed_form_{_x}")
     TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
-    EXPORTS += [f"mc_heston_run_{_x}", f"mc_heston_launch_{_x}", f"mc_heston_paths_{_x}", f"mc_heston_closed_form_{_x}"]
-    EXPORTS += [f"mc_heston_path_run_{_x}", f"mc_heston_path_launch_{_x}", f"mc_heston_path_paths_{_x}"]
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
     TEST_EXPORTS += [f"mc_{_p}_paths_grid_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -292,10 +290,13 @@ def _declare(L: C.CDLL) -> C.CDLL:
         RP = C.POINTER(R)
         getattr(L, f"mc_chol_{X}").argtypes = [C.c_int, RP, RP]
         getattr(L, f"mc_factor_from_cov_{X}").argtypes = [C.c_int, RP, RP, RP]
+        DP = C.POINTER(C.c_double)
+        for prod, S in PRODUCTS.items():
+            head = [ctx, C.POINTER(S[X])] + ([DP] if prod == "american" else [])
+            getattr(L, f"mc_{prod}_launch_{X}").argtypes = head + [u64, u64, u64, C.c_void_p, C.c_void_p]
+            getattr(L, f"mc_{prod}_run_{X}").argtypes = head + [u64, u64, u64, C.POINTER(Result)]
+            getattr(L, f"mc_{prod}_paths_{X}").argtypes = head + [u64, u64, u64, RP]
         for prod, S in (("vanilla", OPTION[X]), ("basket", BASKET[X]), ("cva", CVA[X])):
-            getattr(L, f"mc_{prod}_launch_{X}").argtypes = [ctx, C.POINTER(S), u64, u64, u64, C.c_void_p, C.c_void_p]
-            getattr(L, f"mc_{prod}_run_{X}").argtypes = [ctx, C.POINTER(S), u64, u64, u64, C.POINTER(Result)]
-            getattr(L, f"mc_{prod}_paths_{X}").argtypes = [ctx, C.POINTER(S), u64, u64, u64, RP]
             getattr(L, f"mc_{prod}_run_grid_{X}").argtypes = [ctx, C.POINTER(S), C.c_int, C.c_int, u64, C.POINTER(Result)]
             getattr(L, f"mc_{prod}_paths_grid_{X}").argtypes = [ctx, C.POINTER(S), C.c_int, C.c_int, u64, RP]
         getattr(L, f"mc_normals_{X}").argtypes = [ctx, u64, C.c_uint32, u64, u64, C.c_uint32, RP]
@@ -313,44 +314,16 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_vanilla_greeks2_run_{X}").argtypes = [ctx, C.POINTER(OPTION[X]), u64, u64, u64, C.POINTER(Greeks2)]
         getattr(L, f"mc_vanilla_book_run_{X}").argtypes = [ctx, C.POINTER(BOOK_ENTRY[X]), C.c_int, C.POINTER(Result)]
         getattr(L, f"mc_vanilla_book_launch_{X}").argtypes = [ctx, C.POINTER(BOOK_ENTRY[X]), C.c_int, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_asian_launch_{X}").argtypes = [ctx, C.POINTER(ASIAN[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_asian_run_{X}").argtypes = [ctx, C.POINTER(ASIAN[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_asian_paths_{X}").argtypes = [ctx, C.POINTER(ASIAN[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_asian_control_mean_{X}").argtypes = [C.POINTER(ASIAN[X]), C.POINTER(C.c_double)]
-        getattr(L, f"mc_barrier_launch_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_barrier_run_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_barrier_paths_{X}").argtypes = [ctx, C.POINTER(BARRIER[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_barrier_closed_form_{X}").argtypes = [C.POINTER(BARRIER[X]), C.POINTER(C.c_double)]
-        getattr(L, f"mc_lookback_launch_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_lookback_run_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_lookback_paths_{X}").argtypes = [ctx, C.POINTER(LOOKBACK[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_lookback_closed_form_{X}").argtypes = [C.POINTER(LOOKBACK[X]), C.POINTER(C.c_double)]
-        getattr(L, f"mc_rainbow_launch_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_rainbow_run_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_rainbow_paths_{X}").argtypes = [ctx, C.POINTER(RAINBOW[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_rainbow_closed_form_{X}").argtypes = [C.POINTER(RAINBOW[X]), C.POINTER(C.c_double)]
-        getattr(L, f"mc_autocall_launch_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_autocall_run_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_autocall_paths_{X}").argtypes = [ctx, C.POINTER(AUTOCALL[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_merton_launch_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_merton_run_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_merton_paths_{X}").argtypes = [ctx, C.POINTER(MERTON[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_merton_closed_form_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_double)]
+        getattr(L, f"mc_asian_control_mean_{X}").argtypes = [C.POINTER(ASIAN[X]), DP]
+        getattr(L, f"mc_barrier_closed_form_{X}").argtypes = [C.POINTER(BARRIER[X]), DP]
+        getattr(L, f"mc_lookback_closed_form_{X}").argtypes = [C.POINTER(LOOKBACK[X]), DP]
+        getattr(L, f"mc_rainbow_closed_form_{X}").argtypes = [C.POINTER(RAINBOW[X]), DP]
+        getattr(L, f"mc_merton_closed_form_{X}").argtypes = [C.POINTER(MERTON[X]), DP]
         getattr(L, f"mc_merton_thresholds_{X}").argtypes = [C.POINTER(MERTON[X]), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
-        DP = C.POINTER(C.c_double)
-        getattr(L, f"mc_american_launch_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_american_run_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_american_paths_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), DP, u64, u64, u64, RP]
         getattr(L, f"mc_american_lattice_{X}").argtypes = [C.POINTER(AMERICAN[X]), C.c_int, DP]
         getattr(L, f"mc_american_fit_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), u64, u64, u64, DP, C.POINTER(Result)]
         getattr(L, f"mc_american_fit_date_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), C.c_int, DP, u64, u64, u64, RP, RP, DP]
-        getattr(L, f"mc_heston_launch_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_heston_run_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_heston_paths_{X}").argtypes = [ctx, C.POINTER(HESTON[X]), u64, u64, u64, RP]
-        getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), C.POINTER(C.c_double)]
-        getattr(L, f"mc_heston_path_launch_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, C.c_void_p, C.c_void_p]
-        getattr(L, f"mc_heston_path_run_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, C.POINTER(Result)]
-        getattr(L, f"mc_heston_path_paths_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), u64, u64, u64, RP]
+        getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), DP]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

@@ -29,6 +29,33 @@ def _declared(header):
     return set(re.findall(r"\b(mc_[a-z0-9_]+)\s*\(", text)) - {"mc_context"}
 
 
+def _prototypes(header):
+    """name -> the parameter list between its parentheses, for every function the header declares (comments stripped)"""
+    text = open(os.path.join(INC, header)).read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    return {name: " ".join(params.split())
+            for name, params in re.findall(r"^[A-Za-z_][\w \t\*]*?\b(mc_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text, flags=re.M)}
+
+
+def test_ctypes_prototypes_have_the_declared_number_of_parameters(mc):
+    """Every exported function's argtypes in _lib.py has as many entries as its declaration in the headers has parameters; a
+    function declared (void) has none.  Guards the table-driven launch / run / paths declarations of _lib._declare."""
+    L = mc._lib.lib()
+    protos = {**_prototypes("mc_mi355x.h"), **_prototypes("mc_mi355x_test.h")}
+    names = mc._lib.EXPORTS + mc._lib.TEST_EXPORTS
+    assert len(names) == len(set(names))
+    wrong = {}
+    for name in names:
+        assert name in protos, name
+        argtypes = getattr(L, name).argtypes
+        if protos[name] == "void":
+            if argtypes:
+                wrong[name] = (len(argtypes), 0)
+        elif argtypes is None or len(argtypes) != protos[name].count(",") + 1:
+            wrong[name] = (None if argtypes is None else len(argtypes), protos[name].count(",") + 1)
+    assert not wrong, f"(argtypes, declared parameters) differ: {wrong}"
+
+
 def test_library_exports_every_declared_symbol(mc):
     """The product header declares the drop-in surface, the test header the hooks; the .so exports every one of them."""
     L = mc._lib.lib()
