@@ -20,7 +20,7 @@ import math
 
 import numpy as np
 
-from greeks_ref import NPB, Paths, basket_normals   # noqa: F401  (NPB re-exported for the tests)
+from greeks_ref import NPB, Paths, basket_normals, random_vanilla   # noqa: F401  (NPB re-exported for the tests)
 
 DOMAIN_ASIAN = 4
 
@@ -87,3 +87,9 @@ def black_scholes_call(o):
     d1 = (math.log(s0 / k) + (r + 0.5 * v * v) * t) / sd
     Phi = lambda x: 0.5 * math.erfc(-x / math.sqrt(2.0))
     return s0 * Phi(d1) - k * math.exp(-r * t) * Phi(d1 - sd)
+
+
+# ---- the shapes of the many-trip GPU test (tests/test_gpu_walk_trips.py) --------------------------------------------------------
+TRIP_DATES = [3, 8, 17]        # per path against the model: the ends of the date loops (fp32 4 dates per trip; fp64 8, then 2)
+TRIP_BITS_DATES = [5, 9, 257]  # the same bits on every grid, ranges B and C
+CASES = [random_vanilla(np.random.default_rng(7100 + i)) for i in range(3)]   # asymmetric markets, as the one-trip test draws them

@@ -170,6 +170,10 @@ ATM = dict(s=100.0, k=100.0, r=0.05, v=0.2, t=1.0)
 CASES = [(ATM, 120.0), (dict(s=100.0, k=95.0, r=0.02, v=0.2, t=1.0), 85.0), (dict(s=100.0, k=80.0, r=0.03, v=0.25, t=0.5), 88.0)]
 DATES = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 64, 255, 256, 257, 1000, 4096]   # the last one is MC_MAX_BARRIER_DATES
 N_PATHS = 2121   # eight workgroups and a partial wave
+# the many-trip GPU test (tests/test_gpu_walk_trips.py): per path against the model at the ends of the date loops (fp32 4 dates per
+# trip; fp64 8, then 2), on the path counts of greeks_ref.TRIP_RANGES "A" and "C"; the same bits on every grid on "B" and "C"
+TRIP_DATES = [3, 8, 17]
+TRIP_BITS_DATES = [5, 9, 257]
 
 
 def kinds_of(o, B):

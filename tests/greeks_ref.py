@@ -60,6 +60,53 @@ def kink_free(p, eps):
     return not bool(np.any(p.edge <= eps))
 
 
+def check_sums(est, got, n, what):
+    """{sum, sum2, n} of a run-form call against the same call's per-path dump `got`: the kernels add (double) p and
+    fma((double) p, (double) p, acc) in fp64 in some order, so |sum - S p| <= n 2^-53 S |p| and |sum2 - S p^2| <= (n + 1) 2^-53 S p^2
+    (p^2 is exact inside the device's fma, rounded once on the host), with S taken exactly (math.fsum)."""
+    u = 2.0 ** -53
+    p = [float(x) for x in got]
+    assert est.n == n, what
+    assert abs(est.sum - math.fsum(p)) <= n * u * math.fsum(abs(x) for x in p), (what, est.sum, math.fsum(p))
+    q = math.fsum(x * x for x in p)
+    assert abs(est.sum2 - q) <= (n + 1) * u * q, (what, est.sum2, q)
+
+
+# ---- path ranges on which a lane of a small engine takes several grid-stride trips (tests/test_gpu_walk_trips.py) ------------------
+# A dated product launches min(ceil(n / 256), blocks * 3 / 2) workgroups of 256 lanes per segment of its range:
+#   A  16 blocks (6144 lanes): three full trips, 2125 lanes take a fourth, the last wave is partial (2125 mod 64 = 13)
+#   B  16 blocks, two segments around 2^32 units: the second is written at out + 7000 and runs more than two trips
+#   C  1 block (256 lanes): nine full trips and a partial tenth
+TripRange = namedtuple("TripRange", "blocks first n")
+TRIP_RANGES = {"A": TripRange(16, 4242, 16 * 256 * 5 + 77), "B": TripRange(16, (1 << 32) - 7000, 20_000), "C": TripRange(1, 11, 256 * 9 + 77)}
+TRIP_GROUP = 256
+
+
+def trip_pick(cases, i, name):
+    """The market of the i-th count of a family's TRIP list on range `name`: the family's cases, rotated over counts and ranges."""
+    return cases[(i + "ABC".index(name)) % len(cases)]
+
+
+def trip_lanes(blocks):
+    """The lanes a dated product's launch is capped at on an engine of `blocks` blocks."""
+    return blocks * 3 // 2 * TRIP_GROUP
+
+
+def trip_guard(e, blocks, n_last):
+    """After a dated product's call whose last launch priced n_last paths on the engine e of `blocks` blocks: the launch was capped
+    at the engine's lanes and every lane ran at least two full trips (Engine.last_launch), so that a changed grid rule fails the test
+    instead of turning it back into a one-trip test.  Returns the number of full trips."""
+    grid, group = e.last_launch()
+    assert e.blocks == blocks and grid * group == trip_lanes(blocks) and grid * group * 2 <= n_last, (blocks, grid, group, n_last)
+    return n_last // (grid * group)
+
+
+def trip_last_segment(r):
+    """Paths of the last launch of range r: the part of it beyond the next multiple of 2^32 units, or all of it."""
+    room = (1 << 32) - (r.first & ((1 << 32) - 1))
+    return r.n if r.n <= room else r.n - room
+
+
 # ---- vanilla call -----------------------------------------------------------------------------------------------------
 def vanilla(o, z, lr=False):
     """S_T = S exp((r - v^2/2) T + v sqrt(T) z), payoff (S_T - K)^+.

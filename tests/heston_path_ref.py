@@ -45,6 +45,10 @@ PAYOFF_MUTATIONS = ("late", "one_more", "up_as_down")
 # an odd steps_per_date splits a block; fp64: four pairs per trip, then one); the last three are at MC_MAX_HESTON_STEPS
 SHAPES = [(1, 1), (1, 2), (1, 5), (2, 1), (3, 1), (3, 3), (4, 1), (5, 2), (7, 3), (8, 1), (9, 1), (16, 1), (16, 16), (17, 1), (12, 21), (63, 1),
           (64, 1), (65, 1), (255, 1), (256, 1), (257, 1), (5, 51), (1, 4096), (256, 16), (4096, 1)]
+# the many-trip GPU test (tests/test_gpu_walk_trips.py): per path against the model on the path counts of greeks_ref.TRIP_RANGES "A" and
+# "C"; the same bits on every grid on "B" and "C"
+TRIP_SHAPES = [(3, 1), (5, 2), (16, 1)]
+TRIP_BITS_SHAPES = [(3, 3), (9, 1), (257, 1)]
 FOUR_KIND_SHAPES = [(7, 3), (16, 1)]   # all four barrier types; elsewhere up-and-out at UP and down-and-in at DOWN
 UP, DOWN = 125.0, 80.0
 NEAR_CAP = 0.05

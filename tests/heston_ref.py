@@ -244,6 +244,12 @@ N_PATHS = 2121   # eight workgroups and a partial wave
 N_PATHS_LONG = 329   # one workgroup and a partial wave, from 1024 steps on (the model walks step by step in Python)
 
 
+# the many-trip GPU test (tests/test_gpu_walk_trips.py): per path against the model at the ends of the step loops, on the path counts of
+# greeks_ref.TRIP_RANGES "A" and "C"; the same bits on every grid on "B" and "C"
+TRIP_STEPS = [3, 8, 17]
+TRIP_BITS_STEPS = [5, 9, 257]
+
+
 def n_paths_for(m):
     return N_PATHS if m < 1024 else N_PATHS_LONG
 

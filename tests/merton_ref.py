@@ -281,4 +281,6 @@ HEAVY = (br.ATM, 120.0, dict([("lambda", 4.5), ("mu_j", -0.05), ("delta", 0.1)])
 HEAVY_DATES = [1, 2, 3, 4]
 DATES = br.DATES
 N_PATHS = br.N_PATHS
+TRIP_DATES, TRIP_BITS_DATES = br.TRIP_DATES, br.TRIP_BITS_DATES   # the many-trip GPU test (tests/test_gpu_walk_trips.py)
+TRIP_HEAVY_DATES = 4                                               # ... and its one case on HEAVY
 kinds_of = br.kinds_of

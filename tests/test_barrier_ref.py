@@ -129,13 +129,17 @@ def test_few_paths_carry_a_jump_term(shape_normals, m):
     tolerance; at the fp32 tolerance at most 5 % up to 257 dates and at most 50 % at 1000 and 4096 dates, where the running sum
     W_j is charged its worst case and the GPU test's check of the two possible values is what keeps those paths tested.
     Measured on these shapes: 0 at 1, 1e-3 at 16, 0.03 at 257, 0.16 at 1000, 0.39 at 4096."""
-    z = shape_normals[:, :m]
     cap = 0.05 if m <= 257 else 0.5
-    for o, B in br.CASES:
+    shapes = [(o, B, shape_normals[:, :m]) for o, B in br.CASES]
+    if m in br.TRIP_DATES:   # the shapes of tests/test_gpu_walk_trips.py: the path counts of its ranges, each on the market it rotates to
+        for name in ("A", "C"):
+            o, B = gr.trip_pick(br.CASES, br.TRIP_DATES.index(m), name)
+            shapes.append((o, B, np.random.default_rng(50 + m).standard_normal((gr.TRIP_RANGES[name].n, m))))
+    for o, B, z in shapes:
         for zz in (z, -z):
             p = br.barrier(o, B, m, zz, br.kinds_of(o, B)[0], "discrete")
             share32, share64 = float((p.edge <= TOL["f32"]["pay"]).mean()), float((p.edge <= TOL["f64"]["pay"]).mean())
-            print(f"m={m} B={B}: share of paths with a jump term {share32:.3g} (fp32), {share64:.3g} (fp64)")
+            print(f"m={m} B={B} {len(z)} paths: share of paths with a jump term {share32:.3g} (fp32), {share64:.3g} (fp64)")
             assert share32 <= cap, (o, B, m, share32)
             assert share64 == 0.0, (o, B, m, share64)
             assert not gr.kink_free(p, 1.0)   # the edge is finite: the discrete form does have a step

@@ -15,6 +15,7 @@ import pytest
 
 import asian_ref as ar
 import greeks_ref as gr
+from greeks_ref import trip_guard
 from test_gpu_parity import SEED, TOL
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,15 @@ def mc():
 @pytest.fixture(scope="module")
 def eng(mc):
     e = mc.Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def few(mc):
+    """An engine of 16 blocks: a dated product then runs at most 24 workgroups (6144 lanes), so that a lane of a 300 000-path call
+    takes 48 full grid-stride trips and part of a 49th; on the default engine (3072 workgroups) it takes one below 786 432 paths."""
+    e = mc.Engine(0, blocks=16)
     yield e
     e.close()
 
@@ -77,24 +87,29 @@ def test_every_path_against_the_reference(mc, eng, X, mi):
 
 # ---- 2. sums ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("X", ["f32", "f64"])
-def test_sums_of_a_call_of_many_trips(eng, X):
+def test_sums_of_a_call_of_many_trips(eng, few, X):
+    """On the default engine (one trip a lane at this size) and on the engine of 16 blocks (48 trips a lane and part of a 49th)."""
     m, n, first, chunk = 16, 300_000, 777, 50_000
     o = gr.random_vanilla(np.random.default_rng(99))
     zs = [normals(eng, X, f, min(chunk, first + n - f), m) for f in range(first, first + n, chunk)]
     try:
         for anti, control in ESTIMATORS:
-            estimator(eng, anti, control)
-            g = eng.asian(o, m, n, SEED, first, X)
             parts = [ar.asian(o, m, z, control, anti) for z in zs]
             p = gr.Paths(*(np.concatenate([getattr(q, k) for q in parts], axis=-1) for k in gr.Paths._fields))
             b, v = gr.bound(p, TOL[X]["pay"])[0], p.value[0]
-            assert g.n == v.size == n
             tol, tol2 = b.sum(), (2 * np.abs(v) * b + b * b).sum()
-            print(f"{X} anti={anti} cv={control}: sum err {abs(g.sum - v.sum()):.3g} (tol {tol:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {tol2:.3g})")
-            assert abs(g.sum - v.sum()) <= tol, (anti, control, g.sum, v.sum(), tol)
-            assert abs(g.sum2 - (v * v).sum()) <= tol2, (anti, control, g.sum2, (v * v).sum(), tol2)
+            for e in (eng, few):
+                estimator(e, anti, control)
+                g = e.asian(o, m, n, SEED, first, X)
+                if e is few:
+                    assert trip_guard(e, 16, n) == 48   # full trips a lane
+                assert g.n == v.size == n
+                print(f"{X} anti={anti} cv={control} blocks={e.blocks}: sum err {abs(g.sum - v.sum()):.3g} (tol {tol:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {tol2:.3g})")
+                assert abs(g.sum - v.sum()) <= tol, (anti, control, e.blocks, g.sum, v.sum(), tol)
+                assert abs(g.sum2 - (v * v).sum()) <= tol2, (anti, control, e.blocks, g.sum2, (v * v).sum(), tol2)
     finally:
         estimator(eng, False, False)
+        estimator(few, False, False)
 
 
 # ---- 3. bit rules -----------------------------------------------------------------------------------------------------

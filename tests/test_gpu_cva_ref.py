@@ -14,13 +14,13 @@ Sums are held to the same call's own per-path dump: the values of a call share o
 the host), with S taken exactly (math.fsum).  Every family prints its worst err/bound.
 """
 import contextlib
-import math
 
 import numpy as np
 import pytest
 
 import cva_ref as cr
 import greeks_ref as gr
+from greeks_ref import check_sums
 from test_gpu_parity import SEED
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +29,6 @@ U32 = 1 << 32
 N_PATHS = 3001                 # no multiple of a lane-group count: dead path slots at every lane count
 FIRSTS = (11, U32 - 1000)      # the second crosses the 2^32-unit seam: two segments
 GROUP = 256
-U = 2.0 ** -53
 
 
 # ---- plumbing -------------------------------------------------------------------------------------------------------
@@ -79,14 +78,6 @@ def check_paths(got, p, X, what):
     err = np.abs(got - v)
     assert np.all(err <= bnd), (what, int(np.argmax(err - bnd)), float(err.max()), float(bnd.min()), int((err > bnd).sum()))
     return float(np.max(np.where(err > 0, err / np.where(bnd > 0, bnd, 1.0), 0.0)))
-
-
-def check_sums(est, got, n, what):
-    p = [float(x) for x in got]
-    assert est.n == n, what
-    assert abs(est.sum - math.fsum(p)) <= n * U * math.fsum(abs(x) for x in p), (what, est.sum, math.fsum(p))
-    q = math.fsum(x * x for x in p)
-    assert abs(est.sum2 - q) <= (n + 1) * U * q, (what, est.sum2, q)
 
 
 def models(c, z, X):

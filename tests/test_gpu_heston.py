@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import heston_ref as hr
+from greeks_ref import trip_guard
 from test_gpu_parity import SEED, TOL
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,15 @@ def mc():
 @pytest.fixture(scope="module")
 def eng(mc):
     e = mc.Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def few(mc):
+    """An engine of 16 blocks: a dated product then runs at most 24 workgroups (6144 lanes), so that a lane of a 300 000-path call
+    takes 48 full grid-stride trips and part of a 49th; on the default engine (3072 workgroups) it takes one below 786 432 paths."""
+    e = mc.Engine(0, blocks=16)
     yield e
     e.close()
 
@@ -125,7 +135,8 @@ def test_constant_variance_and_antithetic_identities(eng, X, m):
 
 # ---- 3. sums ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("X", ["f32", "f64"])
-def test_sums_of_a_call_of_many_trips(eng, X):
+def test_sums_of_a_call_of_many_trips(eng, few, X):
+    """On the default engine (one trip a lane at this size) and on the engine of 16 blocks (48 trips a lane and part of a 49th)."""
     m, n, first, chunk = 16, 300_000, 777, 50_000
     tol = TOL[X]["pay"]
     zs = [normals(eng, X, f, min(chunk, first + n - f), m) for f in range(first, first + n, chunk)]
@@ -133,21 +144,24 @@ def test_sums_of_a_call_of_many_trips(eng, X):
         for name, mkt, model in hr.CASES[:2]:
             walks = [hr.walk(mkt, model, m, z1, z2, anti=True) for z1, z2 in zs]
             for anti in (False, True):
-                eng.set_antithetic(anti)
+                eng.set_antithetic(anti), few.set_antithetic(anti)
                 parts = walks if anti else [hr.plain_of(w) for w in walks]
                 v = np.concatenate([p.value[0] for p in parts])
                 b = np.concatenate([hr.bound(p, tol)[0] for p in parts])
-                g = eng.heston(mkt, model, m, n, SEED, first, X)
-                assert g.n == v.size == n
                 t1, t2 = b.sum(), (2 * np.abs(v) * b + b * b).sum()
-                print(f"{X} {name} anti={anti}: sum err {abs(g.sum - v.sum()):.3g} (tol {t1:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {t2:.3g})")
-                assert abs(g.sum - v.sum()) <= t1 and abs(g.sum2 - (v * v).sum()) <= t2, (name, anti)
-                r, t = (float(np.float32(mkt[c])) if X == "f32" else mkt[c] for c in "rt")   # as the precision's struct holds them
-                assert g.expected == pytest.approx(math.exp(-r * t) * g.sum / n, rel=1e-14)
-                dev = math.sqrt((n * g.sum2 - g.sum * g.sum) / (n * (n - 1.0)))
-                assert g.confidence == pytest.approx(1.96 * dev / math.sqrt(n), rel=1e-12)
+                for e in (eng, few):
+                    g = e.heston(mkt, model, m, n, SEED, first, X)
+                    if e is few:
+                        assert trip_guard(e, 16, n) == 48   # full trips a lane
+                    assert g.n == v.size == n
+                    print(f"{X} {name} anti={anti} blocks={e.blocks}: sum err {abs(g.sum - v.sum()):.3g} (tol {t1:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {t2:.3g})")
+                    assert abs(g.sum - v.sum()) <= t1 and abs(g.sum2 - (v * v).sum()) <= t2, (name, anti, e.blocks)
+                    r, t = (float(np.float32(mkt[c])) if X == "f32" else mkt[c] for c in "rt")   # as the precision's struct holds them
+                    assert g.expected == pytest.approx(math.exp(-r * t) * g.sum / n, rel=1e-14)
+                    dev = math.sqrt((n * g.sum2 - g.sum * g.sum) / (n * (n - 1.0)))
+                    assert g.confidence == pytest.approx(1.96 * dev / math.sqrt(n), rel=1e-12)
     finally:
-        eng.set_antithetic(False)
+        eng.set_antithetic(False), few.set_antithetic(False)
 
 
 # ---- 4. bit rules -----------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import pytest
 
 import greeks_ref as gr
 import lookback_ref as lr
+from greeks_ref import trip_guard
 from test_gpu_parity import SEED, TOL
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +38,15 @@ def mc():
 @pytest.fixture(scope="module")
 def eng(mc):
     e = mc.Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def few(mc):
+    """An engine of 16 blocks: a dated product then runs at most 24 workgroups (6144 lanes), so that a lane of a 300 000-path call
+    takes 48 full grid-stride trips and part of a 49th; on the default engine (3072 workgroups) it takes one below 786 432 paths."""
+    e = mc.Engine(0, blocks=16)
     yield e
     e.close()
 
@@ -124,7 +134,8 @@ def test_identities_per_path(eng, X, m):
 
 # ---- 3. sums ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("X", ["f32", "f64"])
-def test_sums_of_a_call_of_many_trips(eng, X):
+def test_sums_of_a_call_of_many_trips(eng, few, X):
+    """On the default engine (one trip a lane at this size) and on the engine of 16 blocks (48 trips a lane and part of a 49th)."""
     m, n, first, chunk = 16, 300_000, 777, 50_000
     o, tol = lr.CASES[1], TOL[X]["pay"]
     zs = [draws(eng, X, f, min(chunk, first + n - f), m) for f in range(first, first + n, chunk)]
@@ -132,19 +143,22 @@ def test_sums_of_a_call_of_many_trips(eng, X):
         for monitoring in lr.MONITORINGS:
             both = [{side: lr.walk(o, m, z, u, side, monitoring, True, tol) for side in (True, False)} for z, u in zs]
             for anti in (False, True):
-                eng.set_antithetic(anti)
+                eng.set_antithetic(anti), few.set_antithetic(anti)
                 for kind in lr.KINDS:
-                    g = eng.lookback(o, m, n, SEED, first, X, kind, monitoring)
                     parts = [lr.value(w[lr.ON_MAX[kind]] if anti else w[lr.ON_MAX[kind]][:1], kind, o["k"]) for w in both]
                     p = gr.Paths(*(np.concatenate([getattr(q, k) for q in parts], axis=-1) for k in gr.Paths._fields))
                     b, v = gr.bound(p, tol)[0], p.value[0]
-                    assert g.n == v.size == n
                     t1, t2 = b.sum(), (2 * np.abs(v) * b + b * b).sum()
-                    print(f"{X} {kind} {monitoring} anti={anti}: sum err {abs(g.sum - v.sum()):.3g} (tol {t1:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {t2:.3g})")
-                    assert abs(g.sum - v.sum()) <= t1, (kind, monitoring, anti, g.sum, v.sum(), t1)
-                    assert abs(g.sum2 - (v * v).sum()) <= t2, (kind, monitoring, anti, g.sum2, (v * v).sum(), t2)
+                    for e in (eng, few):
+                        g = e.lookback(o, m, n, SEED, first, X, kind, monitoring)
+                        if e is few:
+                            assert trip_guard(e, 16, n) == 48   # full trips a lane
+                        assert g.n == v.size == n
+                        print(f"{X} {kind} {monitoring} anti={anti} blocks={e.blocks}: sum err {abs(g.sum - v.sum()):.3g} (tol {t1:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {t2:.3g})")
+                        assert abs(g.sum - v.sum()) <= t1, (kind, monitoring, anti, e.blocks, g.sum, v.sum(), t1)
+                        assert abs(g.sum2 - (v * v).sum()) <= t2, (kind, monitoring, anti, e.blocks, g.sum2, (v * v).sum(), t2)
     finally:
-        eng.set_antithetic(False)
+        eng.set_antithetic(False), few.set_antithetic(False)
 
 
 # ---- 4. bit rules -----------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import pytest
 
 import greeks_ref as gr
 import merton_ref as mr
+from greeks_ref import trip_guard
 from test_gpu_parity import SEED, TOL
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +39,15 @@ def mc():
 @pytest.fixture(scope="module")
 def eng(mc):
     e = mc.Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def few(mc):
+    """An engine of 16 blocks: a dated product then runs at most 24 workgroups (6144 lanes), so that a lane of a 300 000-path call
+    takes 48 full grid-stride trips and part of a 49th; on the default engine (3072 workgroups) it takes one below 786 432 paths."""
+    e = mc.Engine(0, blocks=16)
     yield e
     e.close()
 
@@ -128,26 +138,30 @@ def test_identities_per_path(mc, eng, X, m):
 
 # ---- 3. sums ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("X", ["f32", "f64"])
-def test_sums_of_a_call_of_many_trips(mc, eng, X):
+def test_sums_of_a_call_of_many_trips(mc, eng, few, X):
+    """On the default engine (one trip a lane at this size) and on the engine of 16 blocks (48 trips a lane and part of a 49th)."""
     m, n, first, chunk = 16, 300_000, 777, 50_000
     o, B, jp = mr.CASES[0]
     ds = [draws(mc, eng, X, o, jp, f, min(chunk, first + n - f), m) for f in range(first, first + n, chunk)]
     try:
         for anti in (False, True):
-            eng.set_antithetic(anti)
+            eng.set_antithetic(anti), few.set_antithetic(anti)
             walks = [mr.walk(o, jp, m, z, N, B, True, anti) for z, N in ds]
             for payoff, kind in forms(o, B):
-                g = run(eng, o, jp, B, m, n, first, X, payoff, kind)
                 parts = [mr.value(c, sides, payoff, bool(kind) and kind.endswith("in")) for c, sides in walks]
                 p = gr.Paths(*(np.concatenate([getattr(q, k) for q in parts], axis=-1) for k in gr.Paths._fields))
                 b, v = gr.bound(p, TOL[X]["pay"])[0], p.value[0]
-                assert g.n == v.size == n
                 tol, tol2 = b.sum(), (2 * np.abs(v) * b + b * b).sum()
-                print(f"{X} {payoff} {kind} anti={anti}: sum err {abs(g.sum - v.sum()):.3g} (tol {tol:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {tol2:.3g})")
-                assert abs(g.sum - v.sum()) <= tol, (payoff, kind, anti, g.sum, v.sum(), tol)
-                assert abs(g.sum2 - (v * v).sum()) <= tol2, (payoff, kind, anti, g.sum2, (v * v).sum(), tol2)
+                for e in (eng, few):
+                    g = run(e, o, jp, B, m, n, first, X, payoff, kind)
+                    if e is few:
+                        assert trip_guard(e, 16, n) == 48   # full trips a lane
+                    assert g.n == v.size == n
+                    print(f"{X} {payoff} {kind} anti={anti} blocks={e.blocks}: sum err {abs(g.sum - v.sum()):.3g} (tol {tol:.3g}), sum2 err {abs(g.sum2 - (v * v).sum()):.3g} (tol {tol2:.3g})")
+                    assert abs(g.sum - v.sum()) <= tol, (payoff, kind, anti, e.blocks, g.sum, v.sum(), tol)
+                    assert abs(g.sum2 - (v * v).sum()) <= tol2, (payoff, kind, anti, e.blocks, g.sum2, (v * v).sum(), tol2)
     finally:
-        eng.set_antithetic(False)
+        eng.set_antithetic(False), few.set_antithetic(False)
 
 
 # ---- 4. bit rules -----------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ import pytest
 
 import asian_ref
 import barrier_ref
+import greeks_ref as gr
 import heston_path_ref as hp
 import heston_ref as hr
 from test_gpu_parity import TOL
@@ -136,8 +137,12 @@ def test_caps_hold_on_every_shape_of_the_gpu_test(shape):
     nd, spd = shape
     m = nd * spd
     n = (4 if m < 1024 else 2) * hr.n_paths_for(m)
-    z1, z2 = numpy_normals(m, n, 2000 + m + spd)
-    for name, mkt, model in hr.cases_for(m):
+    shapes = [(case, n) for case in hr.cases_for(m)]
+    if shape in hp.TRIP_SHAPES:   # the shapes of tests/test_gpu_walk_trips.py: the path counts of its ranges, each on the case it rotates to
+        shapes += [(gr.trip_pick(hr.CASES, hp.TRIP_SHAPES.index(shape), name), gr.TRIP_RANGES[name].n) for name in ("A", "C")]
+        assert all(hp.barrier_runs(case[0], X, nd, spd) for case, _ in shapes for X in ("f32", "f64"))
+    for (name, mkt, model), n in shapes:
+        z1, z2 = numpy_normals(m, n, 2000 + m + spd)
         sides = hp.walk(mkt, model, nd, spd, z1, z2, anti=True)
         for X in ("f32", "f64"):
             if not hr.runs(name, X, m):

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import greeks_ref as gr
 import heston_ref as hr
 from test_gpu_parity import TOL
 
@@ -43,8 +44,11 @@ def test_kink_paths_stay_under_the_cap_on_the_shapes_of_the_gpu_test(m):
     """The cap is a condition on the test's shapes, not a measurement: exactly the (case, m, precision) set of the GPU test, on
     numpy normals, both path directions."""
     n = (4 if m < 1024 else 2) * hr.n_paths_for(m)
-    z1, z2 = numpy_normals(m, n, 1000 + m)
-    for name, mkt, model in hr.cases_for(m):
+    shapes = [(case, n) for case in hr.cases_for(m)]
+    if m in hr.TRIP_STEPS:   # the shapes of tests/test_gpu_walk_trips.py: the path counts of its ranges, each on the case it rotates to
+        shapes += [(gr.trip_pick(hr.CASES, hr.TRIP_STEPS.index(m), name), gr.TRIP_RANGES[name].n) for name in ("A", "C")]
+    for (name, mkt, model), n in shapes:
+        z1, z2 = numpy_normals(m, n, 1000 + m)
         p = hr.walk(mkt, model, m, z1, z2, anti=True)
         for X in ("f32", "f64"):
             if not hr.runs(name, X, m):

@@ -189,11 +189,17 @@ def test_reference_model_prices_the_continuous_lookbacks_at_any_date_count(mc, m
 # ---- the scale: sound and sharp ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("m", lr.DATES)
 def test_a_float32_evaluation_stays_inside_the_bound(shape_draws, m):
-    z, u = shape_draws
     tol = TOL["f32"]["pay"]
     assert tol == lr.EPS["f32"] and TOL["f64"]["pay"] == lr.EPS["f64"]
     worst = 0.0
-    for o in lr.CASES:
+    shapes = [(o, shape_draws) for o in lr.CASES]
+    if m in lr.TRIP_DATES:   # the shapes of tests/test_gpu_walk_trips.py: the path counts of its ranges, each on the market it rotates to
+        rng = np.random.default_rng(70 + m)
+        for name in ("A", "C"):
+            n = gr.TRIP_RANGES[name].n
+            draws = rng.standard_normal((n, m)).astype(np.float32), lr.u01_f32(rng.integers(0, 1 << 32, size=(n, m), dtype=np.uint64).astype(np.uint32))
+            shapes.append((gr.trip_pick(lr.CASES, lr.TRIP_DATES.index(m), name), draws))
+    for o, (z, u) in shapes:
         q = rounded(o, "f32")
         for mon in lr.MONITORINGS:
             for anti in (False, True):

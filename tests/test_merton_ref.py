@@ -18,6 +18,7 @@ import pytest
 
 import asian_ref as ar
 import barrier_ref as br
+import greeks_ref as gr
 import merton_ref as mr
 from test_gpu_parity import TOL
 
@@ -306,10 +307,15 @@ def test_the_bound_rejects_a_strict_compare(mc, shape_draws, X, W, m):
 def test_few_paths_are_near_the_barrier(shape_draws, m):
     """Per path direction, the share of paths within the fp32 tolerance of the step (in units of the error of their distance): at
     most 0.05 up to 257 dates and 0.5 at 1000 and 4096; none at the fp64 tolerance."""
-    z = shape_draws
     cap = 0.05 if m <= 257 else 0.5
-    for o, B, jp in shapes(m):
-        N = counts_for(o, jp, m)
+    cases = [(case, shape_draws) for case in shapes(m)]
+    # the shapes of tests/test_gpu_walk_trips.py: the path counts of its ranges, each on the market it rotates to, and HEAVY
+    for name in ("A", "C"):
+        n = gr.TRIP_RANGES[name].n
+        trip = ([gr.trip_pick(mr.CASES, mr.TRIP_DATES.index(m), name)] if m in mr.TRIP_DATES else []) + ([mr.HEAVY] if m == mr.TRIP_HEAVY_DATES else [])
+        cases += [(case, np.random.default_rng(60 + m).standard_normal((n, m))) for case in trip]
+    for (o, B, jp), z in cases:
+        N = counts_for(o, jp, m, len(z))
         _, sides = mr.walk(o, jp, m, z, N, B, B > o["s"], True)
         for s in sides:
             share = float((s["edge"] <= TOL["f32"]["pay"]).mean())
