@@ -235,7 +235,9 @@ int mc_context_device(const mc_context *ctx);
 void *mc_context_stream(const mc_context *ctx);
 int mc_context_blocks(const mc_context *ctx);
 /* Shape of the context's most recent simulation launch: workgroups and lanes per workgroup (0, 0 before the first).  The
- * committed PMC profiles describe launches of one shape; bench.py compares (profiles/pmc_traffic.json "grid_workgroups"). */
+ * committed PMC profiles describe launches of one shape; bench.py compares (profiles/pmc_traffic.json "grid_workgroups").
+ * Under MC_RNG_XORWOW it is the call's one launch, whichever kernel runs it: workgroups x lanes is the L of the sample's
+ * definition below.  (Under Philox the single-unit masked launches at the edges of a vanilla range are not recorded.) */
 int mc_context_last_launch(const mc_context *ctx, int *workgroups, int *group_size);
 /* Name / CU count / clock of the context's device, for logs. */
 int mc_context_info(const mc_context *ctx, char *name, int name_len, int *compute_units, int *clock_mhz);

@@ -1235,8 +1235,11 @@ static int vanilla_enqueue(mc_context *c, const typename VanillaTraits<Real>::In
         if (!out && first % NPB == 0 && end % NPB == 0) {   // whole units only (what the legacy symbols ask for): the hot kernel,
             ProfileScope prof(c);                           // same lanes, same draws, same sums up to fp32 partial-sum order
             if (int rc = T::launch_hot(c, prof, anti, k, w, t, g, st)) return rc;
-        } else if (int rc = launch_vanilla_masked<Real>(c, anti, k, w, t, g, st, out, (Real)scale1))
-            return rc;
+        } else {
+            c->last_grid = g, c->last_group = GROUP;   // the call's one simulation launch: its lanes are the sample's definition
+            if (int rc = launch_vanilla_masked<Real>(c, anti, k, w, t, g, st, out, (Real)scale1))
+                return rc;
+        }
         return finish_call(c, t, g, st);
     }
     std::vector<Segment> segs;
