@@ -233,6 +233,30 @@ def barrier_bound(sides, B, kind, tol):
     return bound / len(sides) + tol * np.abs(barrier(sides, B, kind)), near_any, kink_any
 
 
+def check_asian(got, sides, tol, what):
+    """The per-path rule of the Asian payoff: every value finite, >= 0 and within asian_bound of the model's; the kink paths under
+    heston_ref.KINK_CAP.  Returns (worst error / bound, number of kink paths); asserts."""
+    got = np.asarray(got, dtype=np.float64)
+    assert np.all(np.isfinite(got)) and np.all(got >= 0.0), what
+    b, kink = asian_bound(sides, tol)
+    r = np.abs(got - asian(sides)) / b
+    assert np.all(r <= 1.0), (what, int(np.argmax(r)), float(r.max()))
+    assert kink.sum() <= hr.KINK_CAP * got.size, what
+    return float(r.max()), int(kink.sum())
+
+
+def check_barrier(got, sides, B, kind, tol, what):
+    """The per-path rule of the barrier payoff: every value finite, >= 0 and within its bound of the nearest value the path can take
+    (barrier_errors); the near paths under NEAR_CAP, the kink paths under heston_ref.KINK_CAP.  Returns (worst error / bound, number
+    of near paths, number of kink paths); asserts."""
+    got = np.asarray(got, dtype=np.float64)
+    assert np.all(np.isfinite(got)) and np.all(got >= 0.0), what
+    r, near, kink = barrier_errors(got, sides, B, kind, tol)
+    assert np.all(r <= 1.0), (what, kind, int(np.argmax(r)), float(r.max()))
+    assert near.sum() <= NEAR_CAP * got.size and kink.sum() <= hr.KINK_CAP * got.size, (what, kind)
+    return float(r.max()), int(near.sum()), int(kink.sum())
+
+
 def european_bound(sides, tol):
     """heston_ref's bound of the value at maturity (n_dates = 1 Asian, knock-in + knock-out, a barrier out of reach)."""
     return hr.bound(hr.HestonPaths(european(sides).reshape(1, -1), [s["base"] for s in sides]), tol)
