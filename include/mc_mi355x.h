@@ -79,6 +79,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_AMERICAN_FIT 13u /* the fit of their exercise rule, see mc_american_fit_*: never the paths the rule is priced on */
 #define MC_DOMAIN_RAINBOW 14u /* worst-of / best-of options on a correlated basket walked over dates, see mc_rainbow_run_* */
 #define MC_DOMAIN_AUTOCALL 15u /* worst-of autocallable notes on the same walk, see mc_autocall_run_* */
+#define MC_DOMAIN_LOCALVOL 16u /* calls and puts under a local-volatility surface, see mc_localvol_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -149,6 +150,35 @@ typedef struct { mc_option_f64 option; double v0, kappa, theta, xi, rho; int n_s
 enum { MC_HESTON_PATH_ASIAN = 0, MC_HESTON_PATH_BARRIER = 1 };
 typedef struct { mc_heston_f32 heston; int steps_per_date, payoff, barrier_type; float barrier; } mc_heston_path_f32;
 typedef struct { mc_heston_f64 heston; int steps_per_date, payoff, barrier_type; double barrier; } mc_heston_path_f64;
+
+/* Calls and puts under a local-volatility surface sigma(t, S), log-Euler on n_steps equal steps (see mc_localvol_run_*).  Not in
+ * the reference.  sigma points to n_times rows of n_nodes volatilities: row q holds the surface over the q-th of n_times equal
+ * slices of [0, t], sampled on n_nodes equally spaced nodes of y = ln(S / s) in [y_lo, y_hi].  The array is copied during the
+ * call; no pointer is retained.  The contract has n_dates = n_steps / steps_per_date equally spaced dates.  right gives the
+ * sign of the payoff; barrier_type is one of MC_BARRIER_*; barrier and barrier_type are ignored by the other two payoffs, and
+ * steps_per_date (which must still divide n_steps) by the European one.  option.v is ignored.  The surface travels as
+ * (value, slope) pairs which every workgroup copies into LDS: MC_MAX_LOCALVOL_NODES, the most n_times * n_nodes may be, keeps
+ * that copy at 16 KB in fp32 and 32 KB in fp64. */
+#define MC_MAX_LOCALVOL_STEPS 4096
+#define MC_MAX_LOCALVOL_NODES 2048
+enum { MC_LOCALVOL_EUROPEAN = 0, MC_LOCALVOL_ASIAN = 1, MC_LOCALVOL_BARRIER = 2 };
+enum { MC_LOCALVOL_CALL = 0, MC_LOCALVOL_PUT = 1 };
+typedef struct {
+    mc_option_f32 option;
+    const float *sigma;
+    int n_times, n_nodes;
+    float y_lo, y_hi;
+    int n_steps, steps_per_date, payoff, right, barrier_type;
+    float barrier;
+} mc_localvol_f32;
+typedef struct {
+    mc_option_f64 option;
+    const double *sigma;
+    int n_times, n_nodes;
+    double y_lo, y_hi;
+    int n_steps, steps_per_date, payoff, right, barrier_type;
+    double barrier;
+} mc_localvol_f64;
 
 /* Calls under Merton's jump-diffusion on n_dates equally spaced dates (see mc_merton_run_*): the European call, the
  * arithmetic-average call and the single-barrier call monitored on the dates.  Not in the reference.  lambda is the jump
@@ -586,6 +616,57 @@ int mc_heston_path_launch_f64(mc_context *ctx, const mc_heston_path_f64 *opt, ui
                               double *d_triple, void *stream);
 int mc_heston_path_paths_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
 int mc_heston_path_paths_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+
+/* ---- calls and puts under a local-volatility surface: European, Asian, discretely monitored barrier -------------
+ * dS = r S dt + sigma(t, S) S dW, log-Euler on m = n_steps equal steps: dt = t/m, sdt = sqrt(dt), y = ln(S / s), y_0 = 0, and for
+ * step j = 1 ... m with the step's normal z_j
+ *     sigma_j = surface(slice(j), y_{j-1})
+ *     y_j     = y_{j-1} + (r - sigma_j^2 / 2) dt + sigma_j sdt z_j
+ * The first walk here whose table is read at an index of the lane's own: the volatility depends on the path's state.
+ * The surface is the caller's array sigma[n_times][n_nodes].  Time axis: piecewise constant over n_times >= 1 equal slices of
+ * [0, t]; n_steps must be a multiple of n_times and slice(j) = (j - 1) / (n_steps / n_times) in integers.  Log-spot axis:
+ * n_nodes >= 2 equally spaced nodes of y in [y_lo, y_hi], y_lo < y_hi, linear in y between nodes and flat beyond both ends.
+ * With h = (y_hi - y_lo) / (n_nodes - 1) and a_i = sigma[slice][i]:
+ *     u = clamp((y - y_lo) / h, 0, n_nodes - 1),   i = min(floor(u), n_nodes - 2),   sigma = a_i + (u - i) b_i,   b_i = a_{i+1} - a_i
+ * The interpolant is continuous in y, across the nodes and across the clamps.  b_i is computed in fp64 from the a_i of the call's
+ * precision and rounded once; the kernels evaluate u as fma(y, 1/h, -y_lo/h) with both constants folded in fp64 and rounded once.
+ * The dates are those of mc_heston_path_*: n_dates = n_steps / steps_per_date, date d = 1 ... n_dates falls after step
+ * d * steps_per_date (t_0 is not monitored).  Per path, undiscounted, with S_d = s exp(y_d) and phi = +1 (MC_LOCALVOL_CALL) or -1
+ * (MC_LOCALVOL_PUT):
+ *   MC_LOCALVOL_EUROPEAN   (phi (S_m - k))^+
+ *   MC_LOCALVOL_ASIAN      (phi ((1/n_dates) sum_d S_d - k))^+
+ *   MC_LOCALVOL_BARRIER    g = ln(barrier / s), sgn = +1 (up) or -1 (down), d_d = sgn (g - y_d), P = [min_d d_d > 0];
+ *                          knock-out P (phi (S_m - k))^+, knock-in (1 - P)(phi (S_m - k))^+: value = (c0 + c1 P) payoff.  Monitored
+ *                          on the dates only.
+ * mc_context_set_antithetic: the mean of the value at z and at -z, each direction with its own y and its own lookups; n counts pairs.
+ * Stream: path p is unit p of MC_DOMAIN_LOCALVOL; step j (1-based) draws entry (j-1) % npb of block (j-1) / npb (npb = 4 in
+ * f32, 8 in f64): the Asian layout.  A path's value depends on (seed, global path index, inputs) only.
+ * Path ranges, the finish, call statistics, timing, arming and ordering as for the other products; several GPUs:
+ * mc_localvol_launch_* on the ranges of mc_shard_range, the triples added, mc_closing.
+ * MC_ERR_INVALID before anything is enqueued: n_steps outside [1, MC_MAX_LOCALVOL_STEPS]; n_times < 1, n_nodes < 2 or
+ * n_times * n_nodes > MC_MAX_LOCALVOL_NODES; n_steps not a multiple of n_times; steps_per_date < 1 or not a divisor of n_steps;
+ * sigma NULL, or an entry negative or non-finite; y_lo >= y_hi or either non-finite, or a node spacing so small that 1/h or -y_lo/h
+ * is not finite in the call's precision; payoff, right or (barrier payoff)
+ * barrier_type out of range; for the barrier payoff barrier <= 0 or non-finite, or the spot on or beyond the barrier (up with
+ * s >= barrier, down with s <= barrier); s <= 0, t <= 0, a non-finite s, k, r, t; inputs whose drift and largest volatility over
+ * the m steps are beyond the argument range of the device's exponential (the guard of mc_heston_run_* with max sigma in place of
+ * the variance).  MC_ERR_UNSUPPORTED: the control variate switched on (there is none), a XORWOW context, MC_NORMALS_F32 on the
+ * _f64 calls, a context set up for external normals or the launch geometry.  The context stays usable.
+ * Not offered: continuous monitoring, unequal slices or nodes, rates or dividends that vary in time, several assets, Greeks, a
+ * control variate, a book.  mc_localvol_paths_* returns the per-path values (undiscounted; n_paths <= 2^26).
+ * mc_localvol_sigma_*: the fp64 value of the interpolant above at step `step` (1-based: the slice is slice(step)) and log-spot y,
+ * computed from the table as rounded for that precision (a_i as given, b_i rounded once) with u and the sum in fp64.  Usable
+ * without a GPU; the input checks above, and step outside [1, n_steps] or a non-finite y is MC_ERR_INVALID. */
+int mc_localvol_run_f32(mc_context *ctx, const mc_localvol_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_localvol_run_f64(mc_context *ctx, const mc_localvol_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_localvol_launch_f32(mc_context *ctx, const mc_localvol_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_localvol_launch_f64(mc_context *ctx, const mc_localvol_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                           double *d_triple, void *stream);
+int mc_localvol_paths_f32(mc_context *ctx, const mc_localvol_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_localvol_paths_f64(mc_context *ctx, const mc_localvol_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+int mc_localvol_sigma_f32(const mc_localvol_f32 *opt, int step, double y, double *sigma);
+int mc_localvol_sigma_f64(const mc_localvol_f64 *opt, int step, double y, double *sigma);
 
 /* ---- calls under Merton's jump-diffusion: European, Asian, discretely monitored barrier ----------------------
  * dS/S = (r - lambda kappa) dt + v dW + (J - 1) dN,  N Poisson with rate lambda,  ln J ~ N(mu_j, delta^2),

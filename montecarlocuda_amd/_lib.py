@@ -141,6 +141,17 @@ class HestonPathF64(C.Structure):   # mc_heston_path_f64
     _fields_ = [("heston", HestonF64), ("steps_per_date", C.c_int), ("payoff", C.c_int), ("barrier_type", C.c_int), ("barrier", C.c_double)]
 
 
+def _localvol(O, R):
+    class LocalVol(C.Structure):   # mc_localvol_f32 / mc_localvol_f64
+        _fields_ = [("option", O), ("sigma", C.POINTER(R)), ("n_times", C.c_int), ("n_nodes", C.c_int), ("y_lo", R), ("y_hi", R),
+                    ("n_steps", C.c_int), ("steps_per_date", C.c_int), ("payoff", C.c_int), ("right", C.c_int), ("barrier_type", C.c_int),
+                    ("barrier", R)]
+    return LocalVol
+
+
+LocalVolF32, LocalVolF64 = _localvol(OptionF32, C.c_float), _localvol(OptionF64, C.c_double)
+
+
 class RainbowF32(C.Structure):   # mc_rainbow_f32
     _fields_ = [("basket", BasketF32), ("barrier", C.c_float), ("n_dates", C.c_int), ("type", C.c_int), ("barrier_type", C.c_int)]
 
@@ -206,10 +217,16 @@ HESTON_PATH = {"f32": HestonPathF32, "f64": HestonPathF64}
 RAINBOW = {"f32": RainbowF32, "f64": RainbowF64}
 AUTOCALL = {"f32": AutocallF32, "f64": AutocallF64}
 HESTON_PATH_PAYOFFS = {"asian": 0, "barrier": 1}   # MC_HESTON_PATH_ASIAN, MC_HESTON_PATH_BARRIER
+LOCALVOL = {"f32": LocalVolF32, "f64": LocalVolF64}
+LOCALVOL_PAYOFFS = {"european": 0, "asian": 1, "barrier": 2}   # MC_LOCALVOL_EUROPEAN, MC_LOCALVOL_ASIAN, MC_LOCALVOL_BARRIER
+LOCALVOL_RIGHTS = {"call": 0, "put": 1}                        # MC_LOCALVOL_CALL, MC_LOCALVOL_PUT
+MAX_LOCALVOL_STEPS, MAX_LOCALVOL_NODES = 4096, 2048            # MC_MAX_LOCALVOL_STEPS, MC_MAX_LOCALVOL_NODES
+DOMAIN_LOCALVOL = 16                                           # MC_DOMAIN_LOCALVOL
 # every product has the entry points mc_<product>_launch_*, _run_* and _paths_* over its input struct; the Bermudan ones also take
 # the exercise rule, a const double *, behind the struct
 PRODUCTS = {"vanilla": OPTION, "basket": BASKET, "cva": CVA, "asian": ASIAN, "barrier": BARRIER, "lookback": LOOKBACK, "rainbow": RAINBOW,
-            "autocall": AUTOCALL, "merton": MERTON, "american": AMERICAN, "heston": HESTON, "heston_path": HESTON_PATH}
+            "autocall": AUTOCALL, "merton": MERTON, "american": AMERICAN, "heston": HESTON, "heston_path": HESTON_PATH,
+            "localvol": LOCALVOL}
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -235,6 +252,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_asian_control_mean_{_x}", f"mc_barrier_closed_form_{_x}", f"mc_lookback_closed_form_{_x}", f"mc_rainbow_closed_form_{_x}"]
     EXPORTS += [f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
     EXPORTS.append(f"mc_heston_closed_form_{_x}")
+    EXPORTS.append(f"mc_localvol_sigma_{_x}")
     TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -324,6 +342,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_american_fit_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), u64, u64, u64, DP, C.POINTER(Result)]
         getattr(L, f"mc_american_fit_date_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), C.c_int, DP, u64, u64, u64, RP, RP, DP]
         getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), DP]
+        getattr(L, f"mc_localvol_sigma_{X}").argtypes = [C.POINTER(LOCALVOL[X]), C.c_int, C.c_double, DP]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

@@ -85,7 +85,7 @@ struct mc_context {
     bool timing = true;           // synchronous calls bracket their kernels with HIP events (mc_result.kernel_ms)
     void *d_out = nullptr;        // per-path dump buffer (tests), grown on demand
     size_t d_out_bytes = 0;
-    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a rainbow option's per-date rows, an autocallable note's per-date and per-observation rows, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table
+    CachedTable table{4096, 0};   // the one per-call constant table: CVA per-date rows, an Asian call's per-date xk, a barrier call's per-date dk, a lookback's per-date yk, a rainbow option's per-date rows, an autocallable note's per-date and per-observation rows, a jump-diffusion call's dates, thresholds and s_n, a Bermudan option's per-date rows, a generic basket's folded constants, a basket's Greeks table, a local-volatility surface's (value, slope) pairs
     void *fit_state = nullptr;    // a Longstaff-Schwartz fit's per-path state (W, V), its device table and the fp64 copy of beta: grown on demand
     size_t fit_state_bytes = 0;
     std::vector<char> cva_args;   // the CvaArgs<Real> that go with a cached CVA table (a launch with the same inputs reuses both)
@@ -856,7 +856,7 @@ struct WalkRefusals {
 // what a doubly wrong call reports and whether a refused one touches the table cache: each product keeps its own order.
 template <class Real, class Args, class Before, class Ready, class Pick>
 static int walk_enqueue(mc_context *c, const WalkRefusals &p, uint64_t seed, uint64_t first, uint64_t n, double *d_triple, hipStream_t st,
-                        Real *out, const Args &args, Before before, Ready ready, Pick pick, double unit = 1.0)
+                        Real *out, const Args &args, Before before, Ready ready, Pick pick, double unit = 1.0, size_t dynamic_lds = 0)
 {
     if (c->ext)
         return fail(MC_ERR_UNSUPPORTED, "%s: no external-normals or launch-geometry form", p.name);
@@ -878,7 +878,7 @@ static int walk_enqueue(mc_context *c, const WalkRefusals &p, uint64_t seed, uin
         [&](const Tail &t, const Segment &s, int g, uint64_t done, int) {
             const Work w = context_work(c, seed, s, 0, 0);
             Real *dst = out ? out + done : (Real *)nullptr;
-            launch_sim(prof, kernel, g, st, t, args, w, dst);
+            launch_sim_lds(prof, kernel, g, dynamic_lds, st, t, args, w, dst);
             return MC_OK;
         });
 }
@@ -3044,6 +3044,92 @@ static int heston_path_enqueue(mc_context *c, const typename HestonPath<Real>::I
 }
 
 // ---------------------------------------------------------------------------------------
+// Calls and puts under a local-volatility surface: localvol_kernel, one lane per path, the surface as (value, slope) pairs in LDS
+// ---------------------------------------------------------------------------------------
+template <class Real> struct LocalVol {
+    using In = by_precision<Real, mc_localvol_f32, mc_localvol_f64>;
+    static double discount(const In &o) { return discount_to_maturity(o.option); }
+    static constexpr bool has_control = false;
+    static int check(const In &o) { return by_precision_of<Real>(mc_localvol_check_f32, mc_localvol_check_f64)(&o); }
+};
+
+// The step's and the payoff's constants, folded in fp64 and rounded once (host only: nothing is read but the struct's scalars)
+template <class Real>
+static int localvol_args(const typename LocalVol<Real>::In *v, LocalVolArgs<Real> &args)
+{
+    const auto &o = v->option;
+    const double sc = exp_scale<Real>();
+    const double dt = (double)o.t / (double)v->n_steps;
+    const double h = ((double)v->y_hi - (double)v->y_lo) / (double)(v->n_nodes - 1);
+    const bool barrier = v->payoff == MC_LOCALVOL_BARRIER;
+    const double sgn = barrier && v->barrier_type > MC_BARRIER_UP_IN ? -1.0 : 1.0;
+    const bool in = barrier && (v->barrier_type == MC_BARRIER_UP_IN || v->barrier_type == MC_BARRIER_DOWN_IN);
+    args.n_pairs = v->n_times * v->n_nodes;
+    args.n_nodes = v->n_nodes;
+    args.n_steps = v->n_steps;
+    args.steps_per_slice = v->n_steps / v->n_times;
+    args.steps_per_date = v->steps_per_date;
+    args.inv_h = (Real)(1.0 / h);
+    args.u0 = (Real)(-(double)v->y_lo / h);
+    args.rdt = (Real)((double)o.r * dt);
+    args.mhdt = (Real)(-0.5 * dt);
+    args.sdt = (Real)std::sqrt(dt);
+    args.x0 = (Real)(std::log((double)o.s) * sc);
+    args.strike = o.k;
+    args.phi = v->right == MC_LOCALVOL_PUT ? -1.0f : 1.0f;
+    args.inv_m = (Real)(1.0 / (double)(v->n_steps / v->steps_per_date));
+    args.nsg = (float)-sgn;
+    args.dk = barrier ? (Real)(sgn * std::log((double)v->barrier / (double)o.s)) : (Real)0;
+    args.c0 = in ? 1.0f : 0.0f;
+    args.c1 = in ? -1.0f : 1.0f;
+    return MC_OK;
+}
+
+// The surface as interleaved (a_i, b_i) pairs in the context's table buffer (cached by content, uploaded only when the surface
+// changes): b_i = a_{i+1} - a_i in fp64, rounded once; the last pair of a row carries b = 0 and is never read.  The caller's array is
+// read here, inside the call, and not afterwards.
+template <class Real>
+static int localvol_table_ready(mc_context *c, const typename LocalVol<Real>::In *v, hipStream_t st, LocalVolArgs<Real> &args)
+{
+    static thread_local std::vector<Real> tab;
+    const int nt = v->n_times, nn = v->n_nodes;
+    tab.resize((size_t)nt * nn * 2);
+    for (int q = 0; q < nt; ++q)
+        for (int i = 0; i < nn; ++i) {
+            const size_t at = (size_t)q * nn + i;
+            tab[2 * at] = v->sigma[at];
+            tab[2 * at + 1] = i + 1 < nn ? (Real)((double)v->sigma[at + 1] - (double)v->sigma[at]) : (Real)0;
+        }
+    if (int rc = c->table.upload(c, st, table_key(tab, 'V'), tab.data(), tab.size() * sizeof(Real))) return rc;
+    args.pairs = (const Real *)c->table.d;
+    return MC_OK;
+}
+
+template <class Real>
+static int localvol_enqueue(mc_context *c, const typename LocalVol<Real>::In *v, uint64_t seed, uint64_t first, uint64_t n, double *d_triple,
+                            hipStream_t st, Real *out)
+{
+    LocalVolArgs<Real> args;
+    const size_t lds = (size_t)std::max(v->n_times, 0) * (size_t)std::max(v->n_nodes, 0) * 2 * sizeof(Real);   // checked in before()
+    return walk_enqueue(
+        c, {"localvol", MC_ERR_UNSUPPORTED, MC_ERR_UNSUPPORTED, "localvol: no control variate"}, seed, first, n, d_triple, st, out, args,
+        [&] {
+            if (int rc = LocalVol<Real>::check(*v)) return rc;
+            return localvol_args<Real>(v, args);
+        },
+        [&] { return localvol_table_ready<Real>(c, v, st, args); },
+        [&] {
+            return with_flag(c->antithetic, [&](auto anti) {
+                constexpr bool A = decltype(anti)::value;
+                return v->payoff == MC_LOCALVOL_EUROPEAN ? &localvol_kernel<Real, A, 0>
+                       : v->payoff == MC_LOCALVOL_ASIAN  ? &localvol_kernel<Real, A, 1>
+                                                         : &localvol_kernel<Real, A, 2>;
+            });
+        },
+        1.0, lds);
+}
+
+// ---------------------------------------------------------------------------------------
 // Greeks of the basket call and of the CVA: secondary kernels, plain estimator, synchronous
 // ---------------------------------------------------------------------------------------
 // the inputs' checks and the constant table of basket_greeks_kernel (and, LR = true, of basket_gamma_kernel), uploaded
@@ -3880,6 +3966,7 @@ static int product_paths(mc_context *c, const typename P::In *o, uint64_t seed, 
     MC_DEFINE_AMERICAN_FIT(X, Real)                   \
     MC_ENTRY_POINTS(heston, Heston, X, Real)          \
     MC_ENTRY_POINTS(heston_path, HestonPath, X, Real) \
+    MC_ENTRY_POINTS(localvol, LocalVol, X, Real)      \
     MC_DEFINE_NORMALS(X, Real)
 MC_DEFINE_PRODUCTS(f32, float)
 MC_DEFINE_PRODUCTS(f64, double)

@@ -267,6 +267,7 @@ static double mc_binorm_cdf(double a, double b, double rho)
 #define MERTON mc_merton_f32
 #define AMERICAN mc_american_f32
 #define RAINBOW mc_rainbow_f32
+#define LOCALVOL mc_localvol_f32
 #define MERTON_BITS 32
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -280,6 +281,7 @@ static double mc_binorm_cdf(double a, double b, double rho)
 #undef MERTON
 #undef AMERICAN
 #undef RAINBOW
+#undef LOCALVOL
 #undef MERTON_BITS
 
 #define REAL double
@@ -293,6 +295,7 @@ static double mc_binorm_cdf(double a, double b, double rho)
 #define MERTON mc_merton_f64
 #define AMERICAN mc_american_f64
 #define RAINBOW mc_rainbow_f64
+#define LOCALVOL mc_localvol_f64
 #define MERTON_BITS 64
 #include "mc_hostmath_impl.h"
 #undef REAL
@@ -306,4 +309,5 @@ static double mc_binorm_cdf(double a, double b, double rho)
 #undef MERTON
 #undef AMERICAN
 #undef RAINBOW
+#undef LOCALVOL
 #undef MERTON_BITS

@@ -25,6 +25,9 @@ int mc_american_check_f64(const mc_american_f64 *o);
 /* The input checks of the Heston call, shared by mc_heston_closed_form_* and the GPU entry points (not exported). */
 int mc_heston_check_f32(const mc_heston_f32 *o);
 int mc_heston_check_f64(const mc_heston_f64 *o);
+/* The input checks of the local-volatility products, shared by mc_localvol_sigma_* and the GPU entry points (not exported). */
+int mc_localvol_check_f32(const mc_localvol_f32 *o);
+int mc_localvol_check_f64(const mc_localvol_f64 *o);
 #ifdef __cplusplus
 }
 #endif

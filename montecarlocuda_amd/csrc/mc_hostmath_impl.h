@@ -515,3 +515,78 @@ int FN(mc_american_lattice)(const AMERICAN *o, int steps_per_date, double *price
     *price = p;
     return MC_OK;
 }
+
+/* The inputs every local-volatility entry point refuses (see mc_mi355x.h), the exponent-range guard included: heston_args' rule with
+ * the surface's largest volatility in place of the variance (5e6: the argument range of the device's fp64 exponential; 8.58: the
+ * generator's largest normal).  Internal (mc_hostmath.h): shared with mc_api.hip, not exported. */
+__attribute__((visibility("hidden"))) int FN(mc_localvol_check)(const LOCALVOL *o)
+{
+    const double s = (double)o->option.s, k = (double)o->option.k, r = (double)o->option.r, t = (double)o->option.t;
+    const double y_lo = (double)o->y_lo, y_hi = (double)o->y_hi;
+    if (o->n_steps < 1 || o->n_steps > MC_MAX_LOCALVOL_STEPS)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: n_steps=%d outside [1, %d]", o->n_steps, MC_MAX_LOCALVOL_STEPS);
+    if (o->n_times < 1 || o->n_nodes < 2 || o->n_times > MC_MAX_LOCALVOL_NODES || o->n_nodes > MC_MAX_LOCALVOL_NODES ||
+        (long long)o->n_times * o->n_nodes > MC_MAX_LOCALVOL_NODES)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: need n_times>=1, n_nodes>=2 and n_times * n_nodes <= %d (got %d x %d)",
+                                MC_MAX_LOCALVOL_NODES, o->n_times, o->n_nodes);
+    if (o->n_steps % o->n_times != 0)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: n_times=%d does not divide n_steps=%d", o->n_times, o->n_steps);
+    if (o->steps_per_date < 1 || o->n_steps % o->steps_per_date != 0)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: steps_per_date=%d is below 1 or does not divide n_steps=%d", o->steps_per_date, o->n_steps);
+    if (o->payoff < MC_LOCALVOL_EUROPEAN || o->payoff > MC_LOCALVOL_BARRIER)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: payoff=%d is none of MC_LOCALVOL_EUROPEAN, MC_LOCALVOL_ASIAN, MC_LOCALVOL_BARRIER", o->payoff);
+    if (o->right != MC_LOCALVOL_CALL && o->right != MC_LOCALVOL_PUT)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: right=%d is neither MC_LOCALVOL_CALL nor MC_LOCALVOL_PUT", o->right);
+    if (!isfinite(s) || !isfinite(k) || !isfinite(r) || !isfinite(t) || !isfinite(y_lo) || !isfinite(y_hi))
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: need finite s, k, r, t, y_lo, y_hi");
+    if (!(s > 0) || !(t > 0) || !(y_lo < y_hi))
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: need s>0, t>0, y_lo<y_hi");
+    {   /* the two constants of the lookup, as the kernels hold them: a grid too narrow for REAL leaves 1 / h or -y_lo / h infinite */
+        const double h = (y_hi - y_lo) / (double)(o->n_nodes - 1);
+        if (!isfinite((double)(REAL)(1.0 / h)) || !isfinite((double)(REAL)(-y_lo / h)))
+            return mc_internal_fail(MC_ERR_INVALID, "localvol: the node spacing %g of [y_lo, y_hi] is too small for this precision", h);
+    }
+    if (!o->sigma)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: NULL sigma");
+    double vmax = 0;
+    for (int q = 0; q < o->n_times * o->n_nodes; ++q) {
+        const double a = (double)o->sigma[q];
+        if (!isfinite(a) || !(a >= 0))
+            return mc_internal_fail(MC_ERR_INVALID, "localvol: sigma[%d][%d]=%g is negative or not finite", q / o->n_nodes, q % o->n_nodes, a);
+        vmax = fmax(vmax, a);
+    }
+    double gap = 0;
+    if (o->payoff == MC_LOCALVOL_BARRIER) {
+        BARRIER b = {.option = o->option, .barrier = o->barrier, .n_dates = 1, .type = o->barrier_type, .monitoring = MC_MONITOR_DISCRETE};
+        b.option.v = 0;
+        int rc = FN(mc_barrier_check)(&b, 0);
+        if (rc != MC_OK)
+            return rc;
+        gap = log((double)o->barrier / s);
+    }
+    const double m = (double)o->n_steps, dt = t / m;
+    if (!(fabs(log(s)) + fabs(gap) + fabs(r) * t + m * (0.5 * vmax * vmax * dt + vmax * sqrt(dt) * 8.58) < 5e6))
+        return mc_internal_fail(MC_ERR_INVALID, "localvol: drift and volatility put the simulated spot outside the range of a double");
+    return MC_OK;
+}
+
+/* The interpolant the kernels read at step `step` and log-spot y, in fp64 from the table as rounded for REAL (see mc_mi355x.h). */
+int FN(mc_localvol_sigma)(const LOCALVOL *o, int step, double y, double *sigma)
+{
+    if (!o || !sigma)
+        return mc_internal_fail(MC_ERR_INVALID, "localvol sigma: NULL argument");
+    int rc = FN(mc_localvol_check)(o);
+    if (rc != MC_OK)
+        return rc;
+    if (step < 1 || step > o->n_steps || !isfinite(y))
+        return mc_internal_fail(MC_ERR_INVALID, "localvol sigma: step=%d outside [1, n_steps] or y not finite", step);
+    const REAL *row = o->sigma + (size_t)((step - 1) / (o->n_steps / o->n_times)) * (size_t)o->n_nodes;
+    const double h = ((double)o->y_hi - (double)o->y_lo) / (double)(o->n_nodes - 1);
+    const double u = fmin(fmax((y - (double)o->y_lo) / h, 0.0), (double)(o->n_nodes - 1));
+    int i = (int)floor(u);
+    if (i > o->n_nodes - 2)
+        i = o->n_nodes - 2;
+    const REAL b = (REAL)((double)row[i + 1] - (double)row[i]);
+    *sigma = (double)row[i] + (u - (double)i) * (double)b;
+    return MC_OK;
+}

@@ -3737,6 +3737,193 @@ __global__ __launch_bounds__(GROUP) void heston_path_kernel(const Tail /* first 
 }
 
 // =========================================================================================
+// Calls and puts under a local-volatility surface sigma(t, S): log-Euler on m equal steps (the model is stated in mc_mi355x.h),
+// the European (PAYOFF = 0), the arithmetic-average (1) and the single-barrier payoff monitored on the dates (2).  Not in the
+// reference.  The lane's state is y = ln(S / S0) in natural-log units (the surface is sampled in them) and the step is
+//   u = med3(fma(y, inv_h, u0), 0, n_nodes - 1);  i = min(int(u), n_nodes - 2);  (a, b) = lds[slice + i];  sig = fma(u - i, b, a)
+//   y = fma(sig, sdt z, y + fma(sig sig, -dt/2, r dt))
+// The first walk here whose table index is the LANE's: every other per-call table is indexed by something wave-uniform and comes
+// through scalar loads, this one is a gather.  The surface travels as interleaved (a_i, b_i = a_{i+1} - a_i) pairs (b folded in
+// fp64 on the host and rounded once; the last pair of a row has b = 0 and is never read), which the workgroup copies from the
+// context's constant table into dynamic LDS sized to this call's surface, once, before the grid-stride loop: a lookup is ONE LDS read
+// of 8 bytes (fp32) or 16 bytes (fp64) per direction per step.  The slice is wave-uniform: its base index lives in an SGPR,
+// advanced by a scalar countdown of the steps left in it, exactly as the date's countdown (heston_path_walk).  An odd number of
+// steps per slice or per date puts a boundary between the steps of a block or a pair: both countdowns run after EVERY step.
+//   date:  Asian   acc += E(fma(y, esc, x0)), x0 = ln S0 in exponent units, esc = 1 (f64) or log2 e (f32)
+//          barrier mn = min(mn, fma(nsg, y, dk)), dk = sgn ln(B / S0), nsg = -sgn;  P = [mn > 0] by a select
+//   value: European / barrier (c0 + c1 P) (phi (E(fma(y, esc, x0)) - K))^+;  Asian (phi (acc inv_m - K))^+;  phi = +-1 in an SGPR
+// The date's addend does not depend on the date here (the drift is part of the step), so it is a kernel argument, not a table.
+//   ANTI: a second y walked on -z with its own lookups and its own running sum / minimum; value = mean of the two
+// Stream: domain 16, step j (0-based here) = entry j % NPB of block j / NPB: the Asian layout.
+// =========================================================================================
+template <class Real>
+struct LocalVolArgs {
+    const Real *pairs;       // n_pairs (a, b) pairs, row-major [n_times][n_nodes]
+    int n_pairs, n_nodes;
+    int n_steps, steps_per_slice, steps_per_date;
+    Real inv_h, u0;          // u = clamp(fma(y, inv_h, u0), 0, n_nodes - 1): 1 / h, -y_lo / h
+    Real rdt, mhdt, sdt;     // r dt, -dt / 2, sqrt(dt)
+    Real x0;                 // S = E(fma(y, esc, x0)), esc = exp_units<Real>()
+    Real strike;
+    Real inv_m;              // Asian: 1 / n_dates
+    Real dk;                 // barrier: d = fma(nsg, y, dk), value = (c0 + c1 P) payoff
+    float phi, nsg, c0, c1;  // +-1 and 0: exact in a float, one SGPR each in either precision
+};
+
+// the exponential's units per natural-log unit: exp_model is 2^x in fp32
+template <class Real> __device__ __forceinline__ constexpr Real exp_units() { return sizeof(Real) == 4 ? (Real)1.4426950408889634074 : (Real)1; }
+
+template <class Real> struct LvPair;
+template <> struct LvPair<float> { using type = float2; };
+template <> struct LvPair<double> { using type = double2; };
+
+__device__ __forceinline__ float clamp_r(float u, float hi) { return __builtin_amdgcn_fmed3f(u, 0.0f, hi); }
+__device__ __forceinline__ double clamp_r(double u, double hi) { return min_f64(max0(u), hi); }
+
+template <class Real>
+__device__ __forceinline__ void localvol_step(Real &y, Real zs, const typename LvPair<Real>::type *__restrict__ row, const LocalVolArgs<Real> &o)
+{
+    const Real u = clamp_r(fma_r(y, o.inv_h, o.u0), (Real)(o.n_nodes - 1));
+    int i = (int)u;
+    i = i < o.n_nodes - 2 ? i : o.n_nodes - 2;
+    const auto ab = row[i];
+    const Real sig = fma_r(u - (Real)i, ab.y, ab.x);
+    y = fma_r(sig, zs, y + fma_r(sig * sig, o.mhdt, o.rdt));
+}
+
+template <int PAYOFF, class Real>
+__device__ __forceinline__ void localvol_date(Real y, Real &acc, const LocalVolArgs<Real> &o)
+{
+    if (PAYOFF == 1)
+        acc += exp_model(fma_r(y, exp_units<Real>(), o.x0));
+    else
+        acc = min_r(acc, fma_r((Real)o.nsg, y, o.dk));
+}
+
+template <int PAYOFF, class Real>
+__device__ __forceinline__ Real localvol_value(Real y, Real acc, const LocalVolArgs<Real> &o)
+{
+    const Real level = PAYOFF == 1 ? acc * o.inv_m : exp_model(fma_r(y, exp_units<Real>(), o.x0));
+    const Real a = (Real)o.phi * (level - o.strike);
+    const Real pay = a > 0 ? a : 0;
+    if (PAYOFF != 2)
+        return pay;
+    const Real P = acc > 0 ? (Real)1 : (Real)0;   // the select, as barrier_value
+    return fma_r((Real)o.c1, P, (Real)o.c0) * pay;
+}
+
+// The walk of one path.  step(z) is one Euler step of both directions followed by the two scalar countdowns; the trips differ by
+// precision: fp32 one Philox block = four steps, then one block for the one to three steps left; fp64 four Box-Muller pairs =
+// eight steps (the cursor's phase a compile-time constant in each copy), then one pair per trip, the last of them possibly half used.
+template <bool ANTI, int PAYOFF, class Real, class Gen>
+__device__ __forceinline__ Real localvol_walk(Gen &gen, const LocalVolArgs<Real> &o, const typename LvPair<Real>::type *__restrict__ lds, const Work &w,
+                                              uint32_t c0)
+{
+    const int n = o.n_steps;
+    Real y = 0, y_m = 0;
+    Real acc = PAYOFF == 2 ? (Real)__builtin_inf() : (Real)0, acc_m = acc;
+    int base = 0, s_left = o.steps_per_slice, d_left = o.steps_per_date;   // wave-uniform: SGPRs
+    auto step = [&](Real z) {
+        const Real zs = o.sdt * z;
+        localvol_step(y, zs, lds + base, o);
+        if (ANTI)
+            localvol_step(y_m, -zs, lds + base, o);
+        if (--s_left == 0) {   // wave-uniform
+            base += o.n_nodes;
+            s_left = o.steps_per_slice;
+        }
+        if (PAYOFF != 0 && --d_left == 0) {   // wave-uniform
+            localvol_date<PAYOFF>(y, acc, o);
+            if (ANTI)
+                localvol_date<PAYOFF>(y_m, acc_m, o);
+            d_left = o.steps_per_date;
+        }
+    };
+    if constexpr (sizeof(Real) == 4) {
+        constexpr int NPB = Gen::template npb<float>();
+        static_assert(NPB == 4, "four steps per block");
+        float z[NPB];
+        int j = 0;
+        for (; j + NPB <= n; j += NPB) {
+            gen.normals(w, c0, (uint32_t)(j / NPB), 16u /*MC_DOMAIN_LOCALVOL*/, z);
+            step(z[0]);
+            step(z[1]);
+            step(z[2]);
+            step(z[3]);
+        }
+        if (j < n) {   // wave-uniform: one to three steps left
+            gen.normals(w, c0, (uint32_t)(j / NPB), 16u /*MC_DOMAIN_LOCALVOL*/, z);
+            step(z[0]);
+            if (j + 1 < n)
+                step(z[1]);
+            if (j + 2 < n)
+                step(z[2]);
+        }
+    } else {
+        F64K K;
+        K.load();
+        typename Gen::Carry carry;
+        carry.K = &K;
+        int j = 0;
+        if constexpr (Gen::cursor_phases > 1) {
+#pragma unroll 1
+            for (; j + 8 <= n; j += 8) {
+                uint32_t g4 = (uint32_t)(j >> 3) << 2;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k) {
+                    // heston_path<double>'s tie: a pair's generator call starts after the steps of the pair before it.  Left free, hipcc
+                    // overlaps the four calls of a trip and the antithetic European form needs 129 vector registers: three waves per SIMD
+                    if (ANTI && k)
+                        asm("" : "+v"(y), "+s"(g4));
+                    double z0, z1;
+                    gen.pair(w, c0, 16u /*MC_DOMAIN_LOCALVOL*/, g4 | k, carry, z0, z1);
+                    step(z0);
+                    step(z1);
+                }
+            }
+        }
+#pragma unroll 1
+        for (; j < n; j += 2) {
+            double z0, z1;
+            gen.pair(w, c0, 16u /*MC_DOMAIN_LOCALVOL*/, (uint32_t)(j >> 1), carry, z0, z1);
+            step(z0);
+            if (j + 1 < n)   // wave-uniform
+                step(z1);
+        }
+        gen.pairs_done((uint32_t)((n + 1) >> 1));
+    }
+    Real val = localvol_value<PAYOFF>(y, acc, o);
+    if (ANTI)
+        val = (Real)0.5 * (val + localvol_value<PAYOFF>(y_m, acc_m, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths; dynamic LDS: n_pairs pairs
+template <class Real, bool ANTI, int PAYOFF, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void localvol_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const LocalVolArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    using Pair = typename LvPair<Real>::type;
+    stage_tables<Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Pair *lds = reinterpret_cast<Pair *>(lds_raw);
+    for (int k = threadIdx.x; k < o.n_pairs; k += GROUP)
+        lds[k] = reinterpret_cast<const Pair *>(o.pairs)[k];
+    __syncthreads();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = localvol_walk<ANTI, PAYOFF, Real>(gen, o, lds, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // CVA, parallel in the DATE axis. Reference loop: dp/MonteCarloKernel.cu:241-262 -- one thread walks all N_GRID dates of
 // its path.  With the reformulation above the lane's only state is W_j = z_1 + ... + z_j and everything else is a table
 // row of the date, so the walk is a prefix sum followed by independent work: here a path's dates are shared by

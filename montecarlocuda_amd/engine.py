@@ -215,6 +215,30 @@ def _as_heston_path(X, o, model=None, n_dates=None, steps_per_date=None, payoff=
     return _lib.HESTON_PATH[X](h, int(steps_per_date), payoff, kind, 0.0 if barrier is None else float(barrier))
 
 
+class _LocalVolHolder:
+    """mc_localvol_*: the struct with its surface, a contiguous (n_times, n_nodes) array kept alive for as long as the struct is in
+    use.  An option (OptionData or dict; its v is ignored) with the surface {sigma, y_lo, y_hi}, the contract's n_dates, the Euler
+    steps per date, the payoff ("european", "asian" or "barrier", then with the barrier and its kind) and the right ("call" or
+    "put"), or a dict that carries "sigma", "y_lo", "y_hi", "n_dates", "steps_per_date" and optionally "payoff", "right", "barrier",
+    "kind" itself."""
+
+    def __init__(self, X, o, surface=None, n_dates=None, steps_per_date=None, payoff=None, right="call", barrier=None, kind=None):
+        if surface is None:
+            surface, n_dates, steps_per_date = o, o["n_dates"], o["steps_per_date"]
+            payoff, right = o.get("payoff", "european"), o.get("right", "call")
+            barrier, kind = o.get("barrier"), o.get("kind", "up-and-out")
+        payoff = _lib.LOCALVOL_PAYOFFS[payoff] if isinstance(payoff, str) else int(payoff)
+        right = _lib.LOCALVOL_RIGHTS[right] if isinstance(right, str) else int(right)
+        kind = 0 if kind is None else _lib.BARRIER_TYPES[kind] if isinstance(kind, str) else int(kind)
+        self.sigma = np.ascontiguousarray(surface["sigma"], dtype=NP[X])
+        if self.sigma.ndim != 2:
+            raise ValueError(f"localvol: sigma has shape {self.sigma.shape}, expected (n_times, n_nodes)")
+        opt = _as_option(X, o if not isinstance(o, dict) else dict(o, v=o.get("v", 0.0)))
+        self.struct = _lib.LOCALVOL[X](opt, self.sigma.ctypes.data_as(C.POINTER(_lib.CT[X])), self.sigma.shape[0], self.sigma.shape[1],
+                                       float(surface["y_lo"]), float(surface["y_hi"]), int(n_dates) * int(steps_per_date), int(steps_per_date),
+                                       payoff, right, kind, 0.0 if barrier is None else float(barrier))
+
+
 def _as_merton(X, o, jumps=None, n_dates=None, payoff=None, barrier=None, kind=None) -> C.Structure:
     """mc_merton_*: an option (OptionData or dict) with the jumps {lambda, mu_j, delta}, the contract's n_dates and the payoff
     ("european", "asian" or "barrier", then with the barrier and its kind), or a dict that carries the jumps' three fields,
@@ -549,6 +573,27 @@ class Engine:
         return self._run("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
                          first_path, n_paths)
 
+    def localvol(self, opt, surface, n_steps, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """European call or put under a local-volatility surface, log-Euler on n_steps equal steps (mc_localvol_run_*).  surface:
+        a dict with sigma (an (n_times, n_nodes) array of volatilities over equal time slices and equally spaced nodes of
+        ln(S / s)), y_lo and y_hi; opt's v is ignored.  Honours set_antithetic."""
+        h = _LocalVolHolder(precision, opt, surface, 1, n_steps, "european", right)
+        return self._run("localvol", precision, h.struct, seed, first_path, n_paths)
+
+    def localvol_asian(self, opt, surface, n_dates, steps_per_date, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0,
+                       precision="f64") -> Estimate:
+        """Arithmetic-average call or put over n_dates equally spaced dates under a local-volatility surface, steps_per_date Euler
+        steps between two dates (mc_localvol_run_*).  Honours set_antithetic."""
+        h = _LocalVolHolder(precision, opt, surface, n_dates, steps_per_date, "asian", right)
+        return self._run("localvol", precision, h.struct, seed, first_path, n_paths)
+
+    def localvol_barrier(self, opt, surface, barrier, n_dates, steps_per_date, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0,
+                         precision="f64", kind="up-and-out") -> Estimate:
+        """Single-barrier call or put monitored on n_dates equally spaced dates under a local-volatility surface
+        (mc_localvol_run_*).  kind as for barrier(); there is no continuous monitoring.  Honours set_antithetic."""
+        h = _LocalVolHolder(precision, opt, surface, n_dates, steps_per_date, "barrier", right, barrier, kind)
+        return self._run("localvol", precision, h.struct, seed, first_path, n_paths)
+
     def merton(self, opt, jumps, n_dates, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
         """European call under Merton's jump-diffusion, walked over n_dates equally spaced dates (mc_merton_run_*; exact in law
         at any n_dates, merton_closed_form).  jumps: a dict with lambda, mu_j, delta.  Honours set_antithetic."""
@@ -620,6 +665,9 @@ class Engine:
             return _as_heston(precision, inputs), None
         if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
             return _as_heston_path(precision, inputs), None
+        if prod == "localvol":   # inputs: the option's fields plus "sigma", "y_lo", "y_hi", "n_dates", "steps_per_date" and optionally "payoff", "right", "barrier", "kind"
+            h = _LocalVolHolder(precision, inputs)
+            return h.struct, h
         if prod == "american":   # inputs: the option's fields plus "n_dates", "beta" and optionally "kind", "degree"
             h = _AmericanHolder(precision, inputs, None)
             return h, h
@@ -703,6 +751,20 @@ class Engine:
                              kind="up-and-out"):
         return self._paths("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
                            first_path, n_paths)
+
+    def localvol_paths(self, opt, surface, n_steps, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        h = _LocalVolHolder(precision, opt, surface, 1, n_steps, "european", right)
+        return self._paths("localvol", precision, h.struct, seed, first_path, n_paths)
+
+    def localvol_asian_paths(self, opt, surface, n_dates, steps_per_date, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0,
+                             precision="f64"):
+        h = _LocalVolHolder(precision, opt, surface, n_dates, steps_per_date, "asian", right)
+        return self._paths("localvol", precision, h.struct, seed, first_path, n_paths)
+
+    def localvol_barrier_paths(self, opt, surface, barrier, n_dates, steps_per_date, n_paths, right="call", seed=MC_DEFAULT_SEED,
+                               first_path=0, precision="f64", kind="up-and-out"):
+        h = _LocalVolHolder(precision, opt, surface, n_dates, steps_per_date, "barrier", right, barrier, kind)
+        return self._paths("localvol", precision, h.struct, seed, first_path, n_paths)
 
     def normals(self, seed, domain, first_unit, n_units, block=0, precision="f64"):
         npb = 4 if (precision == "f32" or self._normals_f32) else 8
@@ -892,6 +954,15 @@ def heston_closed_form(opt, model, precision="f64"):
     """Discounted exact price of the European call under the continuous Heston model (no dividend; fp64 quadrature)."""
     p = C.c_double()
     check(getattr(lib(), f"mc_heston_closed_form_{precision}")(C.byref(_as_heston(precision, opt, model, 1)), C.byref(p)))
+    return p.value
+
+
+def localvol_sigma(surface, n_steps, step, y, precision="f64"):
+    """The volatility the engine reads at step `step` (1-based) of n_steps and log-spot y = ln(S / s) on the surface {sigma, y_lo,
+    y_hi}: the interpolant of mc_localvol_run_* in fp64, from the table as rounded for `precision` (mc_localvol_sigma_*; no GPU)."""
+    h = _LocalVolHolder(precision, dict(s=1.0, k=1.0, r=0.0, t=1.0), surface, 1, n_steps, "european")
+    p = C.c_double()
+    check(getattr(lib(), f"mc_localvol_sigma_{precision}")(C.byref(h.struct), int(step), float(y), C.byref(p)))
     return p.value
 
 
