@@ -80,6 +80,7 @@ const char *mc_last_error(void);
 #define MC_DOMAIN_RAINBOW 14u /* worst-of / best-of options on a correlated basket walked over dates, see mc_rainbow_run_* */
 #define MC_DOMAIN_AUTOCALL 15u /* worst-of autocallable notes on the same walk, see mc_autocall_run_* */
 #define MC_DOMAIN_LOCALVOL 16u /* calls and puts under a local-volatility surface, see mc_localvol_run_* */
+#define MC_DOMAIN_HESTON_LEVEL 17u /* the coupled fine and coarse Heston walks of a multilevel correction, see mc_heston_level_run_* */
 
 #define MC_MAX_ASSETS 16         /* basket sizes whose constants can travel as kernel arguments: 1..16 */
 #define MC_MAX_ASSETS_GENERIC 64 /* largest basket: sizes up to 32 have register-resident kernels, 33..64 a generic one */
@@ -616,6 +617,74 @@ int mc_heston_path_launch_f64(mc_context *ctx, const mc_heston_path_f64 *opt, ui
                               double *d_triple, void *stream);
 int mc_heston_path_paths_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
 int mc_heston_path_paths_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+
+/* ---- multilevel Monte Carlo on the Heston walk: one level, the plan, the driver (Giles 2008) ---------------
+ * mc_heston_level_*: the correction of one level, Y = P_fine - P_coarse per path, P the MC_HESTON_PATH_ASIAN payoff (one date:
+ * the European call).  opt describes the FINE walk, exactly that of mc_heston_path_* on m = heston.n_steps steps of dt = t/m.  The
+ * COARSE walk takes m/2 steps of 2 dt, steps_per_date / 2 of them per date, with the same dates, strike and model, on the SAME
+ * Brownian increments: coarse step i = 1 ... m/2 stands on the fine steps a = 2i - 1 and b = 2i.  In the precision of the call,
+ *     t_j = c1 z1_j + c2 z2_j                    the fine step's own (c1 = xi sdt rho, c2 = xi sdt rho', rounded constants)
+ *     W1_i = z1_a + z1_b      rounded once       the increment of the coarse log price, sqrt(2 dt) z1_c = sdt W1_i
+ *     T_i  = t_a + t_b        rounded once       the increment of the coarse variance; W2 = z2_a + z2_b is never formed
+ * and with V the coarse variance, V+ = max(V, 0), s = sqrt(V+):
+ *     x_c += (r - V+/2) 2 dt + s sdt W1_i,       V += kappa (theta - V+) 2 dt + s T_i
+ * where 2 kappa dt, 2 kappa theta dt and 2 (dt/2) are the fine walk's rounded constants doubled (exact).  Date d falls after
+ * coarse step d * steps_per_date / 2 and adds the same per-date constant ln s + r t_d as on the fine walk.
+ * Per path, undiscounted: Y = P_fine - P_coarse.  mc_context_set_antithetic: the mean of Y at (z1, z2) and Y at (-z1, -z2), the
+ * four walks each with their own variance and sums; n counts pairs.  mc_result carries the sums of Y and their closing by mc_closing as
+ * for every product (expected = the discounted mean of Y, which may be negative; confidence = mc_closing's 95 % half-width);
+ * mc_heston_level_paths_* returns the per-path Y (undiscounted; n_paths <= 2^26).
+ * Stream: path p is unit p of MC_DOMAIN_HESTON_LEVEL; FINE step j (1-based) draws entries 2(j-1) % npb and 2(j-1) % npb + 1 of
+ * block 2(j-1) / npb: the Heston layout.  Its own domain makes a level independent of mc_heston_path_* on the same indices; a
+ * path's value depends on (seed, global path index, inputs) only.  Path ranges, the finish, timing, arming and ordering as for
+ * mc_heston_path_*; several GPUs: mc_heston_level_launch_* on the ranges of mc_shard_range, the triples added, mc_closing.
+ * MC_ERR_INVALID before anything is enqueued: everything mc_heston_path_run_* refuses; an odd steps_per_date;
+ * MC_HESTON_PATH_BARRIER (a discontinuous payoff needs another coupling to be worth a level).  MC_ERR_UNSUPPORTED: the control
+ * variate, a XORWOW context, MC_NORMALS_F32 on the _f64 calls, external normals, the launch geometry.  The context stays usable. */
+int mc_heston_level_run_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_level_run_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, mc_result *out);
+int mc_heston_level_launch_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                               double *d_triple, void *stream);
+int mc_heston_level_launch_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths,
+                               double *d_triple, void *stream);
+int mc_heston_level_paths_f32(mc_context *ctx, const mc_heston_path_f32 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, float *h_out);
+int mc_heston_level_paths_f64(mc_context *ctx, const mc_heston_path_f64 *opt, uint64_t seed, uint64_t first_path, uint64_t n_paths, double *h_out);
+
+/* mc_mlmc_plan: the path counts that reach a variance of eps^2 / 2 at least cost, from the levels' variances var[l] and costs
+ * cost[l] per path:  n[l] = ceil(2 eps^-2 sqrt(var[l] / cost[l]) sum_k sqrt(var[k] cost[k])).  Host only, no GPU.  A level of zero
+ * variance gets n = 0.  MC_ERR_INVALID: levels < 1, a NULL pointer, eps <= 0 or not finite, a negative or non-finite variance, a
+ * cost <= 0 or not finite, a count beyond 2^52. */
+int mc_mlmc_plan(int levels, const double *var, const double *cost, double eps, uint64_t *n);
+
+/* mc_heston_mlmc_run_*: the price of the call of `level0` (MC_HESTON_PATH_ASIAN) to a root-mean-square error eps by multilevel
+ * Monte Carlo.  Level 0 is mc_heston_path_run_* on level0 itself; level l >= 1 is mc_heston_level_run_* at heston.n_steps 2^l
+ * steps and steps_per_date 2^l per date.  The algorithm, a pure function of (inputs, seed, the context's antithetic setting):
+ *   1. L = max(min_levels, 2) (at least three levels, so that the bias test below has two corrections); a pilot of n_pilot paths
+ *      on every level 0 ... L;
+ *   2. V_l = the sample variance of level l (discounted), C_0 = n_steps, C_l = 1.5 n_steps 2^l (a cost MODEL, no timer);
+ *      n = mc_mlmc_plan(V, C, eps); every level with n_l above its paths so far is topped up on the NEXT indices of its range, the
+ *      sums added; repeated until no level needs more (the variances move as paths are added);
+ *   3. the weak order fixed at 1: bias = max(|m_L|, |m_{L-1}| / 2), m_l the level's discounted mean; converged if bias <= eps / sqrt 2;
+ *      otherwise, below max_levels, level L + 1 is added with its pilot and step 2 repeats.
+ * Ranges: level 0 owns paths [0, n_0) of MC_DOMAIN_HESTON_PATH; level l >= 1 owns [l 2^40, l 2^40 + n_l) of MC_DOMAIN_HESTON_LEVEL.
+ * No level may pass 2^34 paths, the most of one call (MC_ERR_INVALID: eps is then out of reach).  A level's sums are those of ONE
+ * mc_heston_path_run_* / mc_heston_level_run_* over its final range, up to the order of the fp64 additions.
+ * out: per level its mc_result, with kernel_ms and wall_ms summed over its calls, the paths used and the first path of the range;
+ * price = sum of the means, stderr_ = sqrt(sum_l V_l / n_l) with V_l the sample variance of the DISCOUNTED value of level l
+ * (mc_closing's half-width is that of the undiscounted one), bias as above, converged 1 or 0.  max_levels reached without convergence is NOT an error: converged = 0, MC_OK.
+ * MC_ERR_INVALID before anything is enqueued: what level 0 and level 1 refuse of level0; eps <= 0 or not finite; min_levels < 0;
+ * max_levels < max(min_levels, 2) or > MC_MLMC_MAX_LEVELS; n_pilot < 2 or > 2^34; a finest level max_levels beyond
+ * MC_MAX_HESTON_STEPS.  MC_ERR_UNSUPPORTED as for mc_heston_level_run_*.  The context stays usable. */
+#define MC_MLMC_MAX_LEVELS 12   /* finest level index */
+typedef struct { double eps; int min_levels, max_levels; uint64_t n_pilot; } mc_mlmc_spec;
+typedef struct { mc_result result; uint64_t n_paths, first_path; } mc_mlmc_level;
+typedef struct {
+    double price, stderr_, bias;   /* discounted; stderr_ is one standard error, not the 95 % half-width */
+    int converged, levels;         /* levels = L + 1, the entries of level[] in use */
+    mc_mlmc_level level[MC_MLMC_MAX_LEVELS + 1];
+} mc_mlmc_result;
+int mc_heston_mlmc_run_f32(mc_context *ctx, const mc_heston_path_f32 *level0, const mc_mlmc_spec *spec, uint64_t seed, mc_mlmc_result *out);
+int mc_heston_mlmc_run_f64(mc_context *ctx, const mc_heston_path_f64 *level0, const mc_mlmc_spec *spec, uint64_t seed, mc_mlmc_result *out);
 
 /* ---- calls and puts under a local-volatility surface: European, Asian, discretely monitored barrier -------------
  * dS = r S dt + sigma(t, S) S dW, log-Euler on m = n_steps equal steps: dt = t/m, sdt = sqrt(dt), y = ln(S / s), y_0 = 0, and for

@@ -222,11 +222,29 @@ LOCALVOL_PAYOFFS = {"european": 0, "asian": 1, "barrier": 2}   # MC_LOCALVOL_EUR
 LOCALVOL_RIGHTS = {"call": 0, "put": 1}                        # MC_LOCALVOL_CALL, MC_LOCALVOL_PUT
 MAX_LOCALVOL_STEPS, MAX_LOCALVOL_NODES = 4096, 2048            # MC_MAX_LOCALVOL_STEPS, MC_MAX_LOCALVOL_NODES
 DOMAIN_LOCALVOL = 16                                           # MC_DOMAIN_LOCALVOL
+DOMAIN_HESTON_LEVEL = 17                                       # MC_DOMAIN_HESTON_LEVEL
+MLMC_MAX_LEVELS = 12                                           # MC_MLMC_MAX_LEVELS: the finest level's index
+MLMC_LEVEL_STRIDE, MLMC_MAX_PATHS = 1 << 40, 1 << 34           # level l >= 1 owns paths [l 2^40, l 2^40 + n_l), n_l <= 2^34
+
+
+class MlmcSpec(C.Structure):   # mc_mlmc_spec
+    _fields_ = [("eps", C.c_double), ("min_levels", C.c_int), ("max_levels", C.c_int), ("n_pilot", C.c_uint64)]
+
+
+class MlmcLevel(C.Structure):   # mc_mlmc_level
+    _fields_ = [("result", Result), ("n_paths", C.c_uint64), ("first_path", C.c_uint64)]
+
+
+class MlmcResult(C.Structure):   # mc_mlmc_result
+    _fields_ = [("price", C.c_double), ("stderr_", C.c_double), ("bias", C.c_double), ("converged", C.c_int), ("levels", C.c_int),
+                ("level", MlmcLevel * (MLMC_MAX_LEVELS + 1))]
+
+
 # every product has the entry points mc_<product>_launch_*, _run_* and _paths_* over its input struct; the Bermudan ones also take
 # the exercise rule, a const double *, behind the struct
 PRODUCTS = {"vanilla": OPTION, "basket": BASKET, "cva": CVA, "asian": ASIAN, "barrier": BARRIER, "lookback": LOOKBACK, "rainbow": RAINBOW,
             "autocall": AUTOCALL, "merton": MERTON, "american": AMERICAN, "heston": HESTON, "heston_path": HESTON_PATH,
-            "localvol": LOCALVOL}
+            "localvol": LOCALVOL, "heston_level": HESTON_PATH}   # a level takes the struct of its fine walk
 
 # every symbol include/mc_mi355x.h declares (the drop-in surface), then the test hooks of include/mc_mi355x_test.h;
 # tests/test_abi.py checks that the .so exports each of them and that each is declared in exactly one of the two headers
@@ -237,6 +255,7 @@ EXPORTS = ["mc_last_error", "mc_device_count", "mc_device_pci_bus_id", "mc_conte
            "mc_context_set_normals", "mc_context_set_cva_date_lanes", "mc_basket_control_mean_f32", "mc_basket_control_mean_f64", "mc_closing", "mc_shard_range",
            "mc_chol_f32", "mc_chol_f64", "mc_factor_from_cov_f32", "mc_factor_from_cov_f64"]
 EXPORTS.append("mc_american_solve")
+EXPORTS.append("mc_mlmc_plan")
 TEST_EXPORTS = ["mc_xorwow_words", "mc_words", "mc_grid_normals", "mc_context_set_grid_form", "mc_math_probe"]
 # mc_math_probe (include/mc_mi355x_test.h): operations, and 64-bit words per item in and out
 PROBE_OPS = {"neg2log": 0, "sincos": 1, "exp": 2, "sqrt": 3, "recip": 4, "u01": 5, "pair": 6, "f32_block": 7}
@@ -253,6 +272,7 @@ for _x in ("f32", "f64"):
     EXPORTS += [f"mc_merton_closed_form_{_x}", f"mc_merton_thresholds_{_x}", f"mc_american_lattice_{_x}", f"mc_american_fit_{_x}"]
     EXPORTS.append(f"mc_heston_closed_form_{_x}")
     EXPORTS.append(f"mc_localvol_sigma_{_x}")
+    EXPORTS.append(f"mc_heston_mlmc_run_{_x}")
     TEST_EXPORTS.append(f"mc_american_fit_date_{_x}")
     TEST_EXPORTS.append(f"mc_normals_{_x}")
     TEST_EXPORTS += [f"mc_{_p}_from_normals_{_x}" for _p in ("vanilla", "basket", "cva")]
@@ -295,6 +315,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.mc_xorwow_words.argtypes = [ctx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.mc_math_probe.argtypes = [ctx, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
     L.mc_american_solve.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
+    L.mc_mlmc_plan.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(u64)]
     for X in ("f32", "f64"):
         getattr(L, f"mc_basket_control_mean_{X}").argtypes = [C.POINTER(BASKET[X]), C.POINTER(C.c_double)]
     L.mc_context_profile.argtypes = [ctx, C.c_int]
@@ -343,6 +364,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         getattr(L, f"mc_american_fit_date_{X}").argtypes = [ctx, C.POINTER(AMERICAN[X]), C.c_int, DP, u64, u64, u64, RP, RP, DP]
         getattr(L, f"mc_heston_closed_form_{X}").argtypes = [C.POINTER(HESTON[X]), DP]
         getattr(L, f"mc_localvol_sigma_{X}").argtypes = [C.POINTER(LOCALVOL[X]), C.c_int, C.c_double, DP]
+        getattr(L, f"mc_heston_mlmc_run_{X}").argtypes = [ctx, C.POINTER(HESTON_PATH[X]), C.POINTER(MlmcSpec), u64, C.POINTER(MlmcResult)]
         getattr(L, f"mc_basket_gamma_run_{X}").argtypes = [ctx, C.POINTER(BASKET[X]), u64, u64, u64, C.POINTER(Result), C.POINTER(Result)]
     return L
 

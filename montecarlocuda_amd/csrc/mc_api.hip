@@ -3044,6 +3044,47 @@ static int heston_path_enqueue(mc_context *c, const typename HestonPath<Real>::I
 }
 
 // ---------------------------------------------------------------------------------------
+// One level of a multilevel estimator on the Heston walk: heston_level_kernel, a fine and a coarse walk per lane, one set of normals
+// ---------------------------------------------------------------------------------------
+template <class Real> struct HestonLevel : HestonPath<Real> {};
+
+// what a level asks beyond mc_heston_path_*: a continuous payoff, and fine steps that pair up inside every date
+template <class Real>
+static int heston_level_check(const typename HestonLevel<Real>::In &v)
+{
+    if (int rc = heston_path_check<Real>(v)) return rc;
+    if (v.payoff != MC_HESTON_PATH_ASIAN)
+        return fail(MC_ERR_INVALID, "heston level: the barrier payoff is discontinuous: halving the step does not shrink its correction's variance fast enough to be worth a level");
+    if (v.steps_per_date % 2 != 0)
+        return fail(MC_ERR_INVALID, "heston level: steps_per_date=%d is odd: a coarse step is two fine steps and a date falls on both walks", v.steps_per_date);
+    return MC_OK;
+}
+
+// the fine walk's constants and table are heston_path's; the coarse walk's are the same numbers with kdt, ktdt and av doubled
+template <class Real>
+static int heston_level_enqueue(mc_context *c, const typename HestonLevel<Real>::In *v, uint64_t seed, uint64_t first, uint64_t n,
+                                double *d_triple, hipStream_t st, Real *out)
+{
+    HestonLevelArgs<Real> args;
+    return walk_enqueue(
+        c, {"heston level", MC_ERR_UNSUPPORTED, MC_ERR_UNSUPPORTED, "heston level: no control variate"}, seed, first, n, d_triple, st, out, args,
+        [&] {
+            if (int rc = heston_level_check<Real>(*v)) return rc;
+            return heston_args<Real>(&v->heston, args.f.h);
+        },
+        [&]() -> int {
+            if (int rc = heston_path_table_ready<Real>(c, v, st, args.f)) return rc;
+            args.c = args.f;
+            args.c.h.n_steps = args.f.h.n_steps / 2;
+            args.c.steps_per_date = args.f.steps_per_date / 2;
+            args.c.h.kdt = 2 * args.f.h.kdt, args.c.h.ktdt = 2 * args.f.h.ktdt;
+            args.c.h.av = 2 * args.f.h.av, args.c.av = 2 * args.f.av;
+            return MC_OK;
+        },
+        [&] { return with_flag(c->antithetic, [&](auto anti) { return &heston_level_kernel<Real, decltype(anti)::value>; }); });
+}
+
+// ---------------------------------------------------------------------------------------
 // Calls and puts under a local-volatility surface: localvol_kernel, one lane per path, the surface as (value, slope) pairs in LDS
 // ---------------------------------------------------------------------------------------
 template <class Real> struct LocalVol {
@@ -3967,9 +4008,126 @@ static int product_paths(mc_context *c, const typename P::In *o, uint64_t seed, 
     MC_ENTRY_POINTS(heston, Heston, X, Real)          \
     MC_ENTRY_POINTS(heston_path, HestonPath, X, Real) \
     MC_ENTRY_POINTS(localvol, LocalVol, X, Real)      \
+    MC_ENTRY_POINTS(heston_level, HestonLevel, X, Real) \
     MC_DEFINE_NORMALS(X, Real)
 MC_DEFINE_PRODUCTS(f32, float)
 MC_DEFINE_PRODUCTS(f64, double)
+
+// ---------------------------------------------------------------------------------------
+// The multilevel driver: host only, every number from the calls above
+// ---------------------------------------------------------------------------------------
+extern "C" int mc_mlmc_plan(int levels, const double *var, const double *cost, double eps, uint64_t *n)
+{
+    if (levels < 1 || !var || !cost || !n)
+        return fail(MC_ERR_INVALID, "mlmc plan: levels < 1 or a NULL pointer");
+    if (!(eps > 0) || !std::isfinite(eps))
+        return fail(MC_ERR_INVALID, "mlmc plan: need a finite eps > 0");
+    double total = 0.0;
+    for (int l = 0; l < levels; ++l) {
+        if (!(var[l] >= 0) || !std::isfinite(var[l]))
+            return fail(MC_ERR_INVALID, "mlmc plan: the variance of level %d is negative or not finite", l);
+        if (!(cost[l] > 0) || !std::isfinite(cost[l]))
+            return fail(MC_ERR_INVALID, "mlmc plan: the cost of level %d is not a finite number > 0", l);
+        total += std::sqrt(var[l] * cost[l]);
+    }
+    for (int l = 0; l < levels; ++l) {
+        const double want = std::ceil(2.0 / (eps * eps) * std::sqrt(var[l] / cost[l]) * total);
+        if (!(want <= 0x1p52))
+            return fail(MC_ERR_INVALID, "mlmc plan: level %d needs more than 2^52 paths", l);
+        n[l] = (uint64_t)want;
+    }
+    return MC_OK;
+}
+
+static constexpr uint64_t MLMC_LEVEL_STRIDE = 1ull << 40, MLMC_MAX_PATHS = 1ull << 34;
+
+template <class Real>
+static int heston_mlmc_run(mc_context *c, const typename HestonPath<Real>::In *level0, const mc_mlmc_spec *spec, uint64_t seed, mc_mlmc_result *out)
+{
+    using In = typename HestonPath<Real>::In;
+    if (!c || !level0 || !spec || !out)
+        return fail(MC_ERR_INVALID, "heston mlmc: NULL argument");
+    const int first_top = std::max(spec->min_levels, 2);
+    if (!(spec->eps > 0) || !std::isfinite(spec->eps) || spec->min_levels < 0 || spec->max_levels < first_top || spec->max_levels > MC_MLMC_MAX_LEVELS ||
+        spec->n_pilot < 2 || spec->n_pilot > MLMC_MAX_PATHS)
+        return fail(MC_ERR_INVALID, "heston mlmc: need eps > 0, 0 <= min_levels, max(min_levels, 2) <= max_levels <= %d, 2 <= n_pilot <= 2^34", MC_MLMC_MAX_LEVELS);
+    auto at_level = [&](int l) {
+        In v = *level0;
+        v.heston.n_steps = level0->heston.n_steps << l, v.steps_per_date = level0->steps_per_date << l;
+        return v;
+    };
+    // what the calls themselves refuse, ahead of the first of them: level 0 as it is, level 1 for the payoff, the finest level for its steps
+    if (int rc = heston_path_check<Real>(*level0)) return rc;
+    if ((int64_t)level0->heston.n_steps << spec->max_levels > MC_MAX_HESTON_STEPS)
+        return fail(MC_ERR_INVALID, "heston mlmc: level %d takes %lld steps, beyond MC_MAX_HESTON_STEPS", spec->max_levels,
+                    (long long)((int64_t)level0->heston.n_steps << spec->max_levels));
+    {
+        const In v1 = at_level(1);
+        if (int rc = heston_level_check<Real>(v1)) return rc;
+    }
+    *out = mc_mlmc_result{};
+    const double disc = HestonPath<Real>::discount(*level0);
+    double var[MC_MLMC_MAX_LEVELS + 1], cost[MC_MLMC_MAX_LEVELS + 1];
+    // paths [first_path + n_paths, first_path + n_paths + more) of level l, its sums added to what the level holds
+    auto extend = [&](int l, uint64_t more) -> int {
+        mc_mlmc_level &lv = out->level[l];
+        if (lv.n_paths + more > MLMC_MAX_PATHS)
+            return fail(MC_ERR_INVALID, "heston mlmc: level %d needs %llu paths, more than the 2^34 of one call: eps is out of reach", l,
+                        (unsigned long long)(lv.n_paths + more));
+        const In v = at_level(l);
+        mc_result r;
+        const int rc = l == 0 ? product_run<HestonPath<Real>, heston_path_enqueue<Real>>(c, &v, seed, lv.first_path + lv.n_paths, more, &r)
+                              : product_run<HestonLevel<Real>, heston_level_enqueue<Real>>(c, &v, seed, lv.first_path + lv.n_paths, more, &r);
+        if (rc) return rc;
+        lv.result.sum += r.sum, lv.result.sum2 += r.sum2, lv.result.kernel_ms += r.kernel_ms, lv.result.wall_ms += r.wall_ms;
+        lv.n_paths += more;
+        lv.result.n = lv.n_paths;
+        mc_closing(lv.result.sum, lv.result.sum2, lv.result.n, disc, &lv.result.expected, &lv.result.confidence);
+        // the sample variance of the DISCOUNTED value (mc_closing's half-width is that of the undiscounted one)
+        const double dn = (double)lv.n_paths;
+        var[l] = disc * disc * std::max(dn * lv.result.sum2 - lv.result.sum * lv.result.sum, 0.0) / (dn * (dn - 1.0));
+        return MC_OK;
+    };
+    auto open_level = [&](int l) -> int {
+        out->level[l].first_path = (uint64_t)l * MLMC_LEVEL_STRIDE;
+        cost[l] = (l == 0 ? 1.0 : 1.5) * (double)level0->heston.n_steps * (double)(1u << l);
+        return extend(l, spec->n_pilot);
+    };
+    int L = first_top;
+    for (int l = 0; l <= L; ++l)
+        if (int rc = open_level(l)) return rc;
+    for (;;) {
+        for (bool grew = true; grew;) {
+            uint64_t want[MC_MLMC_MAX_LEVELS + 1];
+            if (int rc = mc_mlmc_plan(L + 1, var, cost, spec->eps, want)) return rc;
+            grew = false;
+            for (int l = 0; l <= L; ++l)
+                if (want[l] > out->level[l].n_paths) {
+                    if (int rc = extend(l, want[l] - out->level[l].n_paths)) return rc;
+                    grew = true;
+                }
+        }
+        out->bias = std::max(std::fabs(out->level[L].result.expected), 0.5 * std::fabs(out->level[L - 1].result.expected));
+        out->converged = out->bias <= spec->eps / std::sqrt(2.0);
+        if (out->converged || L == spec->max_levels)
+            break;
+        ++L;
+        if (int rc = open_level(L)) return rc;
+    }
+    out->levels = L + 1;
+    double v = 0.0;
+    for (int l = 0; l <= L; ++l) {
+        out->price += out->level[l].result.expected;
+        v += var[l] / (double)out->level[l].n_paths;
+    }
+    out->stderr_ = std::sqrt(v);
+    return MC_OK;
+}
+
+extern "C" int mc_heston_mlmc_run_f32(mc_context *c, const mc_heston_path_f32 *level0, const mc_mlmc_spec *spec, uint64_t seed, mc_mlmc_result *out)
+{ return heston_mlmc_run<float>(c, level0, spec, seed, out); }
+extern "C" int mc_heston_mlmc_run_f64(mc_context *c, const mc_heston_path_f64 *level0, const mc_mlmc_spec *spec, uint64_t seed, mc_mlmc_result *out)
+{ return heston_mlmc_run<double>(c, level0, spec, seed, out); }
 
 // The raw Philox words of blocks first_block ... first_block + n_blocks - 1 of each unit (test hook, mc_mi355x_test.h)
 extern "C" int mc_words(mc_context *c, uint64_t seed, uint32_t domain, uint64_t first_unit, uint64_t n_units, uint32_t first_block,

@@ -3737,6 +3737,173 @@ __global__ __launch_bounds__(GROUP) void heston_path_kernel(const Tail /* first 
 }
 
 // =========================================================================================
+// One level of a multilevel estimator on the Heston walk: Y = P_fine - P_coarse, P the Asian payoff of heston_path_kernel (one date:
+// the European call).  Not in the reference.  A lane walks the fine path on m steps of dt and the coarse path on m / 2 steps of
+// 2 dt on the SAME Brownian increments, the normals drawn once: with the fine steps 2i - 1 and 2i of coarse step i,
+//   W1 = z1_a + z1_b,  T = t_a + t_b        (t_j = fma(z2_j, c2, c1 z1_j), the fine steps' own; both sums rounded once)
+// and sqrt(2 dt) z_c = sqrt(dt) W, so the coarse step is heston_step on (W1, T) with the fine walk's c1, c2 and aw and with
+// kdt, ktdt and av doubled (exact doublings of the fine walk's rounded constants: `c` below differs from `f` in nothing else).
+// The date countdown is shared and counts coarse steps: steps_per_date is even, a date falls after steps_per_date / 2 of them, and
+// both legs read the same addend through the same scalar load.
+//   ANTI: four walks -- fine and coarse on (z, T), fine and coarse on (-z, -T) -- value = mean of the two differences
+// Stream: domain 17, the Heston layout of the FINE walk.
+// =========================================================================================
+template <class Real>
+struct HestonLevelArgs {
+    HestonPathArgs<Real> f, c;   // the fine walk (heston_path_kernel's arguments) and the coarse one
+};
+
+// what a lane carries per direction: the two legs and their running sums over the dates
+template <class Real>
+struct HestonLevelSide {
+    HestonSide<Real> f, c;
+    Real acc_f, acc_c;
+};
+
+template <class Real>
+__device__ __forceinline__ void heston_level_date(HestonLevelSide<Real> &s, Real addend, const HestonLevelArgs<Real> &o)
+{
+    heston_date<0>(s.f, s.acc_f, addend, o.f);
+    heston_date<0>(s.c, s.acc_c, addend, o.c);
+}
+
+template <class Real>
+__device__ __forceinline__ Real heston_level_value(const HestonLevelSide<Real> &s, const HestonLevelArgs<Real> &o)
+{
+    return heston_path_value<0>(s.f, s.acc_f, o.f) - heston_path_value<0>(s.c, s.acc_c, o.c);
+}
+
+// fp32: one Philox block = two fine steps = exactly one coarse step; a trip is a block
+template <bool ANTI, class Gen>
+__device__ __forceinline__ float heston_level_walk(Gen &gen, const HestonLevelArgs<float> &o, const Work &w, uint32_t c0)
+{
+    constexpr int NPB = Gen::template npb<float>();
+    static_assert(NPB == 4, "two fine steps per block");
+    const int n = o.f.h.n_steps;   // even
+    const HestonSide<float> start = {o.f.h.v0, 0.0f, 0.0f};
+    HestonLevelSide<float> p = {start, start, 0.0f, 0.0f}, q = p;
+    float z[NPB];
+    int d = 0, left = o.c.steps_per_date;
+    for (int j = 0; j < n; j += 2) {
+        gen.normals(w, c0, (uint32_t)(j >> 1), 17u /*MC_DOMAIN_HESTON_LEVEL*/, z);
+        const float ta = __builtin_fmaf(z[1], o.f.h.c2, o.f.h.c1 * z[0]);
+        const float tb = __builtin_fmaf(z[3], o.f.h.c2, o.f.h.c1 * z[2]);
+        const float W1 = z[0] + z[2], T = ta + tb;
+        heston_step(p.f, z[0], ta, o.f.h, 0.0f);
+        heston_step(p.f, z[2], tb, o.f.h, 0.0f);
+        heston_step(p.c, W1, T, o.c.h, 0.0f);
+        if (ANTI) {
+            heston_step(q.f, -z[0], -ta, o.f.h, 0.0f);
+            heston_step(q.f, -z[2], -tb, o.f.h, 0.0f);
+            heston_step(q.c, -W1, -T, o.c.h, 0.0f);
+        }
+        if (--left == 0) {   // wave-uniform
+            const float addend = o.f.tab[d];
+            heston_level_date(p, addend, o);
+            if (ANTI)
+                heston_level_date(q, addend, o);
+            ++d;
+            left = o.c.steps_per_date;
+        }
+    }
+    float val = heston_level_value(p, o);
+    if (ANTI)
+        val = 0.5f * (val + heston_level_value(q, o));
+    return val;
+}
+
+// fp64: heston_path_walk<double>'s trips.  Four pairs = four fine steps = two coarse steps, taken after the second and the fourth
+// pair; m = 2 (mod 4) leaves one coarse step, taken on phases 0 and 1 of the cursor (compile-time constants again).
+template <bool ANTI, class Gen>
+__device__ __forceinline__ double heston_level_walk(Gen &gen, const HestonLevelArgs<double> &o, const Work &w, uint32_t c0)
+{
+    static_assert(Gen::cursor_phases == 4, "a coarse step is half a trip of the pair cursor");
+    const int n = o.f.h.n_steps;   // even
+    const HestonSide<double> start = {o.f.h.v0, 0.0, 0.0};
+    HestonLevelSide<double> p = {start, start, 0.0, 0.0}, q = p;
+    const double floor = 0x1p-1000;
+    F64K K;
+    K.load();
+    typename Gen::Carry carry;
+    carry.K = &K;
+    double W1 = 0.0, T = 0.0;
+    auto fine =[&](double z1, double z2, bool second) {
+        const double t = __builtin_fma(z2, o.f.h.c2, o.f.h.c1 * z1);
+        heston_step(p.f, z1, t, o.f.h, floor);
+        if (ANTI)
+            heston_step(q.f, -z1, -t, o.f.h, floor);
+        W1 = second ? W1 + z1 : z1;
+        T = second ? T + t : t;
+    };
+    int d = 0, left = o.c.steps_per_date;
+    auto coarse = [&]() {
+        heston_step(p.c, W1, T, o.c.h, floor);
+        if (ANTI)
+            heston_step(q.c, -W1, -T, o.c.h, floor);
+        if (--left == 0) {   // wave-uniform
+            const double addend = o.f.tab[d];
+            heston_level_date(p, addend, o);
+            if (ANTI)
+                heston_level_date(q, addend, o);
+            ++d;
+            left = o.c.steps_per_date;
+        }
+    };
+    int j = 0;
+#pragma unroll 1
+    for (; j + 4 <= n; j += 4) {
+        uint32_t g4 = (uint32_t)(j >> 2) << 2;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            // heston_path<double>'s tie: a step's generator call starts after the variance of the step before it
+            if (ANTI && k)
+                asm("" : "+v"(p.f.V), "+s"(g4));
+            double z0, z1;
+            gen.pair(w, c0, 17u /*MC_DOMAIN_HESTON_LEVEL*/, g4 | k, carry, z0, z1);
+            fine(z0, z1, k & 1u);
+            if (k & 1u)
+                coarse();
+        }
+    }
+    if (j < n) {   // wave-uniform: m = 2 (mod 4), the last coarse step
+        uint32_t g4 = (uint32_t)(j >> 2) << 2;
+#pragma unroll
+        for (uint32_t k = 0; k < 2; ++k) {
+            if (ANTI && k)
+                asm("" : "+v"(p.f.V), "+s"(g4));
+            double z0, z1;
+            gen.pair(w, c0, 17u /*MC_DOMAIN_HESTON_LEVEL*/, g4 | k, carry, z0, z1);
+            fine(z0, z1, k & 1u);
+        }
+        coarse();
+    }
+    gen.pairs_done((uint32_t)n);
+    double val = heston_level_value(p, o);
+    if (ANTI)
+        val = 0.5 * (val + heston_level_value(q, o));
+    return val;
+}
+
+// one lane per path, grid-stride over the segment's paths
+template <class Real, bool ANTI, class Gen = GenPhilox>
+__global__ __launch_bounds__(GROUP) void heston_level_kernel(const Tail /* first argument, read late: mc_reduce.hpp */, const HestonLevelArgs<Real> o, const Work w, Real *__restrict__ out)
+{
+    stage_tables<Real>();
+    const uint32_t stride = gridDim.x * GROUP;
+    double acc_s = 0.0, acc_q = 0.0;
+    Gen gen(w);
+    for (uint32_t i = blockIdx.x * GROUP + threadIdx.x; i < w.n_units; i += stride) {
+        const Real p = heston_level_walk<ANTI>(gen, o, w, w.unit_lo + i);
+        acc_s += (double)p;
+        acc_q = __builtin_fma((double)p, (double)p, acc_q);
+        if (out)  // wave-uniform: per-path dump for the parity tests
+            out[i] = p;
+    }
+    group_sum2(acc_s, acc_q);
+    finish_group(acc_s, acc_q);
+}
+
+// =========================================================================================
 // Calls and puts under a local-volatility surface sigma(t, S): log-Euler on m equal steps (the model is stated in mc_mi355x.h),
 // the European (PAYOFF = 0), the arithmetic-average (1) and the single-barrier payoff monitored on the dates (2).  Not in the
 // reference.  The lane's state is y = ln(S / S0) in natural-log units (the surface is sampled in them) and the step is

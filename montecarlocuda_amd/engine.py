@@ -73,6 +73,22 @@ class Estimate:
         return OptionValue(self.expected, self.confidence)
 
 
+@dataclass
+class MlmcLevel:
+    estimate: Estimate      # the level's sums and their closing; kernel_ms and wall_ms summed over its calls
+    n_paths: int
+    first_path: int
+
+
+@dataclass
+class MlmcEstimate:         # mc_mlmc_result
+    price: float
+    stderr: float           # one standard error of the discounted price
+    bias: float             # max(|m_L|, |m_{L-1}| / 2)
+    converged: bool
+    levels: list
+
+
 def _as_option(X, o) -> C.Structure:
     if isinstance(o, dict):
         o = OptionData(**{k: o[k] for k in "skrvt"})
@@ -573,6 +589,23 @@ class Engine:
         return self._run("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
                          first_path, n_paths)
 
+    def heston_level(self, opt, model, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
+        """One multilevel correction on the Heston walk (mc_heston_level_run_*): Y = P_fine - P_coarse of the Asian call (n_dates = 1:
+        the European call), the fine walk on n_dates * steps_per_date steps (steps_per_date even), the coarse walk on half of them, on
+        the same Brownian increments.  `expected` is the discounted mean of Y.  Honours set_antithetic."""
+        return self._run("heston_level", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "asian"), seed, first_path, n_paths)
+
+    def heston_mlmc(self, opt, model, n_dates, steps_per_date, eps, seed=MC_DEFAULT_SEED, precision="f64", min_levels=2, max_levels=8,
+                    n_pilot=10_000) -> "MlmcEstimate":
+        """The call of heston_asian(opt, model, n_dates, steps_per_date, ...) priced to a root-mean-square error eps by multilevel
+        Monte Carlo (mc_heston_mlmc_run_*): level 0 on n_dates * steps_per_date steps, level l on 2^l times as many."""
+        spec = _lib.MlmcSpec(float(eps), int(min_levels), int(max_levels), int(n_pilot))
+        r = _lib.MlmcResult()
+        struct = _as_heston_path(precision, opt, model, n_dates, steps_per_date, "asian")
+        check(getattr(lib(), f"mc_heston_mlmc_run_{precision}")(self._ctx, C.byref(struct), C.byref(spec), seed, C.byref(r)))
+        levels = [MlmcLevel(_estimate(r.level[l].result), int(r.level[l].n_paths), int(r.level[l].first_path)) for l in range(r.levels)]
+        return MlmcEstimate(r.price, r.stderr_, r.bias, bool(r.converged), levels)
+
     def localvol(self, opt, surface, n_steps, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0, precision="f64") -> Estimate:
         """European call or put under a local-volatility surface, log-Euler on n_steps equal steps (mc_localvol_run_*).  surface:
         a dict with sigma (an (n_times, n_nodes) array of volatilities over equal time slices and equally spaced nodes of
@@ -665,6 +698,8 @@ class Engine:
             return _as_heston(precision, inputs), None
         if prod == "heston_path":   # inputs: those of "heston" without "n_steps", plus "n_dates", "steps_per_date", "payoff", ("barrier", "kind")
             return _as_heston_path(precision, inputs), None
+        if prod == "heston_level":   # inputs: those of "heston_path" (the fine walk; "payoff" optional, "asian" if given; steps_per_date even)
+            return _as_heston_path(precision, dict(inputs, payoff=inputs.get("payoff", "asian"))), None
         if prod == "localvol":   # inputs: the option's fields plus "sigma", "y_lo", "y_hi", "n_dates", "steps_per_date" and optionally "payoff", "right", "barrier", "kind"
             h = _LocalVolHolder(precision, inputs)
             return h.struct, h
@@ -751,6 +786,9 @@ class Engine:
                              kind="up-and-out"):
         return self._paths("heston_path", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "barrier", barrier, kind), seed,
                            first_path, n_paths)
+
+    def heston_level_paths(self, opt, model, n_dates, steps_per_date, n_paths, seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
+        return self._paths("heston_level", precision, _as_heston_path(precision, opt, model, n_dates, steps_per_date, "asian"), seed, first_path, n_paths)
 
     def localvol_paths(self, opt, surface, n_steps, n_paths, right="call", seed=MC_DEFAULT_SEED, first_path=0, precision="f64"):
         h = _LocalVolHolder(precision, opt, surface, 1, n_steps, "european", right)
@@ -948,6 +986,18 @@ def american_lattice(opt, n_dates, steps_per_date, kind="put", precision="f64"):
     p = C.c_double()
     check(getattr(lib(), f"mc_american_lattice_{precision}")(C.byref(_as_american(precision, opt, n_dates, kind, 3)), int(steps_per_date), C.byref(p)))
     return p.value
+
+
+def mlmc_plan(var, cost, eps):
+    """Path counts per level for a variance of eps^2 / 2 at least cost (mc_mlmc_plan; host only):
+    n_l = ceil(2 eps^-2 sqrt(V_l / C_l) sum_k sqrt(V_k C_k))."""
+    var, cost = np.ascontiguousarray(var, dtype=np.float64), np.ascontiguousarray(cost, dtype=np.float64)
+    if var.ndim != 1 or var.shape != cost.shape:
+        raise ValueError(f"var and cost have shapes {var.shape} and {cost.shape}, expected two vectors of one length")
+    n = np.zeros(var.size, dtype=np.uint64)
+    DP = C.POINTER(C.c_double)
+    check(lib().mc_mlmc_plan(int(var.size), var.ctypes.data_as(DP), cost.ctypes.data_as(DP), float(eps), n.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return [int(x) for x in n]
 
 
 def heston_closed_form(opt, model, precision="f64"):
