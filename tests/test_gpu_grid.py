@@ -132,9 +132,17 @@ def test_streams_match_oracle(eng, po, G, T, count):
     assert len({r.tobytes() for r in flat}) == G * T
 
 
-# the last four make the fused kernels cut every thread's stream into 32, 2, 2 and 8 pieces (mc_api.hip: grid_pieces)
 GEOMS = [(1, 1, 1), (1, 64, 64), (3, 64, 200), (4, 100, 37), (2, 256, 1000), (5, 7, 1001), (2, 1024, 5000), (3, 128, 7),
          (1, 64, 70000), (3, 100, 9001), (2, 256, 20000), (4, 128, 33001)]
+# the pieces the fused kernels cut every thread's stream into (mc_launch_shape.hpp: grid_pieces), asserted on the launch itself
+PIECES = dict(zip(GEOMS, [1, 1, 1, 1, 1, 8, 1, 1, 32, 4, 4, 16]))
+PIECES.update({(2, 10, 33): 1, (1, 256, 100): 1, (2, 64, 4100): 4, (1, 32, 8200): 16, (3, 32, 70): 1, (2, 32, 1100): 2})
+
+
+def assert_pieces(eng, G, T, per_block):
+    """After a fused call: one workgroup per (block, piece) of whole waves (Engine.last_launch)."""
+    grid, group = eng.last_launch()
+    assert (grid, group) == (G * PIECES[(G, T, per_block)], (T + 63) // 64 * 64), (G, T, per_block, grid, group)
 
 
 @pytest.mark.parametrize("X", ["f32", "f64"])
@@ -143,6 +151,7 @@ def test_vanilla_grid_is_the_hot_kernel_on_the_reference_arrangement(mc, eng, po
     streams = eng.grid_normals(G, T, po.grid_draws_per_thread(T, per_block, 1))
     z = po.grid_path_normals(streams, per_block, 1).reshape(-1).astype(NP[X])       # dp: the float normal widened
     e, fused = both_forms(eng, "vanilla", VAN, G, T, per_block, X)
+    assert_pieces(eng, G, T, per_block)
     h, vals = eng.vanilla_from_normals(VAN, z, X)
     assert e.n == G * per_block == h.n
     assert (e.sum, e.sum2) == (h.sum, h.sum2)
@@ -156,10 +165,12 @@ def test_vanilla_grid_is_the_hot_kernel_on_the_reference_arrangement(mc, eng, po
 def test_basket_grid_carries_the_kept_normal_across_paths(mc, eng, po, X, n_assets):
     """Odd asset counts: a path's last Box-Muller pair is split with the next path of the same thread."""
     b = basket_inputs(mc, n_assets, X)
-    for G, T, per_block in ((3, 64, 200), (2, 10, 33), (1, 256, 100), (2, 64, 4100), (1, 32, 8200)):   # the last two: 2 and 8 pieces per thread
+    for G, T, per_block in ((3, 64, 200), (2, 10, 33), (1, 256, 100), (2, 64, 4100), (1, 32, 8200)):   # the last two: 4 and 16 pieces per thread
         streams = eng.grid_normals(G, T, po.grid_draws_per_thread(T, per_block, n_assets))
         g = po.grid_path_normals(streams, per_block, n_assets).astype(NP[X])
         e, fused = both_forms(eng, "basket", b, G, T, per_block, X, fused_exists=n_assets <= 16)
+        if n_assets <= 16:
+            assert_pieces(eng, G, T, per_block)
         h, vals = eng.basket_from_normals(b, g, X)
         assert e.n == G * per_block
         assert (e.sum, e.sum2) == (h.sum, h.sum2), (G, T, per_block)
@@ -183,6 +194,7 @@ def test_cva_grid_draws_only_for_the_dates_that_draw(mc, eng, po, X, n_grid):
         z = np.zeros((G * per_block, n_grid), dtype=NP[X])
         z[:, :draws] = po.grid_path_normals(streams, per_block, draws)
         e, fused = both_forms(eng, "cva", c, G, T, per_block, X)
+        assert_pieces(eng, G, T, per_block)
         h, vals = eng.cva_from_normals(c, z, X)
         assert (e.sum, e.sum2, e.n) == (h.sum, h.sum2, G * per_block)
         want, o = po.dev_cva_on_normals(X, c, z.astype(np.float64), 0)
