@@ -1,4 +1,4 @@
-"""Wide, asymmetric markets for the nine dated families (not a test module): the market lists and the helpers that
+"""Wide, asymmetric markets for the eleven dated families (not a test module): the market lists and the helpers that
 tests/test_wide_markets.py (no GPU: conditions on the lists, power) and tests/test_gpu_wide_markets.py (every path of every
 instantiation against the family's float64 model) share.
 
@@ -10,7 +10,7 @@ once by a seeded generator ON A FIXED TABLE OF STRATA (the rows of `_single`'s t
 stable, so the lists are frozen: a market that breaks a condition of tests/test_wide_markets.py is replaced by editing its row, within
 its stratum), every value rounded to a float32 so that the model and the kernels of both precisions read the same number:
 
-  single-asset families (Asian, barrier, lookback, Merton, Heston, Heston path, Bermudan), 12 markets each:
+  single-asset families (Asian, barrier, lookback, Merton, Heston, Heston path, Bermudan, local vol, Heston level), 12 markets each:
     spot        near 0.05, exactly 1.0 (ln S0 = 0), tens, above 1e4
     volatility  near 0.03, near 0.2, above 1               (Heston: sqrt(v0))
     maturity    days (near 0.01), about 1 but not 1, decades (near 20)
@@ -25,6 +25,17 @@ its stratum), every value rounded to a float32 so that the model and the kernels
     Merton      mu_j of both signs, delta = 0 and 0.4, lambda t from 0.05 to 6 (lambda dt = 6 at one date: the 64-bit table's cap is
                 reached at 6.23)
     Bermudan    puts and calls; the rule of (market, dates) is american_ref.fit on 2^13 paths of a fixed numpy stream, cached
+    local vol   the row plus a surface scaled to the row's v and t (the product ignores the option's v).  Grid [y_lo, y_hi] =
+                c + (lo, hi) v sqrt t, (lo, hi) rotating over (-2.2, 1.1) (straddling 0, unequal arms), (0.3, 2.0) (wholly above 0: every
+                path starts in the lower clamp) and (-1.8, -0.2) (wholly below: in the upper clamp); c = drift / 2, held inside the
+                interval that keeps the placement where the drift dwarfs v sqrt t (LV_CENTRE).  Values v (1 + 0.15 q / n_times - 0.35 x
+                + 0.25 x^2 + 0.1 / (n_nodes - 1) cos(2.3 i + 0.7 q)), x from -1 to 1 over the nodes: rows and intervals all differ, the
+                slope in y times sqrt(dt) z stays of order 1 at any v and t; one market's values are multiplied by (1 + x) / 2 and reach
+                exactly 0 at the first node.  A second barrier p standard deviations on the other side: every market runs the four
+                kinds.  Calls and puts, the three payoffs, shapes (n_steps, n_times, steps_per_date, n_nodes) LV_SHAPES
+    Heston level  the Heston row with a strike chosen for a DIFFERENCE Y = P_fine - P_coarse: q at most 0 (both legs in the money on
+                half the paths and more; far out of the money Y is exactly 0), k = 0 and k < 0 on two markets (Y = A_fine - A_coarse
+                on every path), q = 0.5 on two (the kink between the legs); shapes (n_dates, steps_per_date) LEVEL_SHAPES
   rainbow and autocall, n = 1 ... 8, two markets each: greeks_ref.random_basket's manner -- distinct spots over 0.05 to 3e4, unequal
     absolute weights (not 1 / s_i), volatilities 0.05 to 0.8 in random order, a random correlation with a negative entry factored by
     mc.chol, t in {0.08, 1.3, 7}, r of both signs; strike, barrier, triggers and coupon levels in standard deviations of the initial
@@ -36,7 +47,8 @@ its stratum), every value rounded to a float32 so that the model and the kernels
 `cases(family, market, m, X, eng)` yields every call the GPU test makes on one market at one date count -- antithetic off and on, the
 family's switches -- as a Case: how to run it, the model's values, and the family's OWN per-path rule (imported from where it
 lives: test_gpu_barrier.check_paths, test_gpu_lookback.check_paths, merton_ref.check_paths, test_gpu_heston.check,
-heston_path_ref.check_asian / check_barrier, test_gpu_american.check_paths, test_gpu_rainbow.check_paths, autocall_ref.check).  `eng` is
+heston_path_ref.check_asian / check_barrier, test_gpu_american.check_paths, test_gpu_rainbow.check_paths, autocall_ref.check,
+localvol_ref.check / check_barrier, heston_level_ref.check).  `eng` is
 an Engine, or a NumpyEngine: the same call signature for normals and words, numpy's generator behind it, so that the CPU test
 walks exactly the shapes of the GPU test.
 """
@@ -51,8 +63,10 @@ import asian_ref as ar
 import autocall_ref as ac
 import barrier_ref as br
 import greeks_ref as gr
+import heston_level_ref as hl
 import heston_path_ref as hp
 import heston_ref as hr
+import localvol_ref as lv
 import lookback_ref as lr
 import merton_ref as mr
 import rainbow_ref as rr
@@ -66,12 +80,24 @@ from test_gpu_rainbow import check_paths as rainbow_check_paths
 N_PATHS = 2121                                  # eight workgroups and a partial wave
 FIRSTS = (0, 12345, (1 << 32) - 1000)           # the last range crosses the 2^32-unit seam
 DATES = [1, 3, 8, 17]                           # the ends of the date loops (fp32 4 dates per trip; fp64 8, then 2): TRIP_DATES and one date
-SINGLE = ["asian", "barrier", "lookback", "merton", "heston", "heston_path", "american"]
+SINGLE = ["asian", "barrier", "lookback", "merton", "heston", "heston_path", "american", "localvol", "heston_level"]
 MULTI = ["rainbow", "autocall"]
 FAMILIES = SINGLE + MULTI
-BARRIER_FAMILIES = ["barrier", "merton", "heston_path", "rainbow", "autocall"]
+BARRIER_FAMILIES = ["barrier", "merton", "heston_path", "rainbow", "autocall", "localvol"]
 NEAR_CAP = KINK_CAP = 0.05
-assert hp.NEAR_CAP == NEAR_CAP and hr.KINK_CAP == KINK_CAP
+assert hp.NEAR_CAP == NEAR_CAP and hr.KINK_CAP == KINK_CAP and lv.NEAR_CAP == NEAR_CAP
+NPX = {"f32": np.float32, "f64": np.float64}
+# local vol, (n_steps, n_times, steps_per_date, n_nodes): the ends of both precisions' step loops (fp32 four steps per block; fp64 eight
+# per trip, then two), one slice and one per step, 2 nodes and the 65 of the family's own test, and an odd number of steps per slice (3)
+# and per date (5) that differ
+LV_SHAPES = [(1, 1, 1, 2), (3, 3, 1, 3), (8, 2, 2, 65), (17, 1, 1, 9), (15, 5, 5, 4)]
+LV_GRIDS = [("straddle", -2.2, 1.1), ("above", 0.3, 2.0), ("below", -1.8, -0.2)]
+LV_CENTRE = {"straddle": (-0.8, 1.5), "above": (-0.2, math.inf), "below": (-math.inf, 0.1)}   # the centre c in units of v sqrt t: the placement holds
+IN_PLACEMENT = {"straddle": lambda g: g[0] < 0 < g[1], "above": lambda g: g[0] > 0, "below": lambda g: g[1] < 0}
+LV_ZERO_NODE = 6                                # the market whose surface is 0 at its first node
+# Heston level, (n_dates, steps_per_date): m = 2 (mod 4) and m = 0 (mod 4), one coarse step per date, a date inside an fp64 trip and in the remainder
+LEVEL_SHAPES = [(1, 2), (3, 2), (1, 6), (2, 10), (8, 4), (17, 2)]
+LEVEL_OTM = (7, 10)                             # the two markets kept out of the money, q = 0.5
 
 
 def f32(x):
@@ -152,6 +178,45 @@ def _heston(seed, rows=None):
         o["k"] = f32(o["s"] * math.exp(o["r"] * t - 0.5 * w * t + mk["q"] * sd))
         mk["B_up"], mk["B_down"] = f32(o["s"] * math.exp(mk["p"] * sd + max(o["r"] * t, 0.0))), f32(o["s"] * math.exp(-mk["p"] * sd + min(o["r"] * t - 0.5 * w * t, 0.0)))
     return out
+
+
+def _localvol(seed):
+    """The row plus a grid and a second barrier on the other side; the surface of a shape is surface_of(mk, shape)."""
+    out = _non_positive_strikes(_single(seed))
+    for i, mk in enumerate(out):
+        o = mk["o"]
+        drift, sd = (o["r"] - 0.5 * o["v"] ** 2) * o["t"], o["v"] * math.sqrt(o["t"])
+        name, lo, hi = LV_GRIDS[i % 3]
+        c = min(max(0.5 * drift, LV_CENTRE[name][0] * sd), LV_CENTRE[name][1] * sd)
+        side = -1 if mk["up"] else 1
+        mk.update(placement=name, grid=(f32(c + lo * sd), f32(c + hi * sd)), zero_node=i == LV_ZERO_NODE,
+                  B2=f32(o["s"] * math.exp(side * mk["p"] * sd + (drift if drift * side > 0 else 0.0))))
+    return out
+
+
+def surface_of(mk, shape):
+    """The surface of a local-vol market at a shape, every value a float32 (module docstring); a market may carry its own rule
+    (`surface`: the old fixed cases, the mirrored grid of the power test)."""
+    if "surface" in mk:
+        return mk["surface"](shape)
+    _, nt, _, nn = shape
+    q, i = np.arange(nt)[:, None], np.arange(nn)[None, :]
+    x = np.linspace(-1.0, 1.0, nn)[None, :]
+    a = mk["o"]["v"] * (1.0 + 0.15 * q / nt - 0.35 * x + 0.25 * x * x + 0.1 / (nn - 1) * np.cos(2.3 * i + 0.7 * q))
+    if mk["zero_node"]:
+        a = a * (0.5 * (1.0 + x))
+    return lv.make_surface(a.astype(np.float32).astype(np.float64), *mk["grid"])
+
+
+def _heston_level(seed):
+    """The Heston rows, struck for a difference: q at most 0, but 0.5 on LEVEL_OTM; k = 0 and k < 0 on two more."""
+    out = _heston(seed)
+    for i, mk in enumerate(out):
+        o, md = mk["o"], mk["model"]
+        mk["qk"] = 0.5 if i in LEVEL_OTM else min(mk["q"], 0.0)
+        w = 0.5 * (md["v0"] + md["theta"]) if md["kappa"] > 0 else md["v0"]
+        o["k"] = f32(o["s"] * math.exp(o["r"] * o["t"] - 0.5 * w * o["t"] + mk["qk"] * math.sqrt(w * o["t"])))
+    return _non_positive_strikes(out)
 
 
 def _merton(seed):
@@ -277,15 +342,20 @@ def markets(family):
             "asian": lambda: _non_positive_strikes(_single(1)), "barrier": lambda: _non_positive_strikes(_single(2)), "lookback": lambda: _single(3),
             "merton": lambda: _merton(4), "heston": lambda: _non_positive_strikes(_heston(5)),
             "heston_path": lambda: _non_positive_strikes(_heston(6)),
-            "american": lambda: _american(7), "rainbow": _rainbow, "autocall": _autocall}[family]()
+            "american": lambda: _american(7), "localvol": lambda: _localvol(8), "heston_level": lambda: _heston_level(9),
+            "rainbow": _rainbow, "autocall": _autocall}[family]()
         assert len(_MARKETS[family]) <= 16
     return _MARKETS[family]
 
 
 def dates_of(family, mk):
-    """The date counts of one market, Heston path: (dates, steps per date)."""
+    """The date counts of one market, Heston path and Heston level: (dates, steps per date), local vol: LV_SHAPES."""
     if family == "heston_path":
         return [(nd, spd) for nd in DATES for spd in (1, 2)]
+    if family == "localvol":
+        return LV_SHAPES
+    if family == "heston_level":
+        return LEVEL_SHAPES
     return RAINBOW_DATES[mk["n"]] if family in MULTI else DATES
 
 
@@ -309,13 +379,14 @@ def _ratio(err, b):
         return np.where(err == 0, 0.0, err / b)
 
 
-def _case(tag, anti, run, check, value, bound, near=None, kink=None, knocked=None, control=False):
+def _case(tag, anti, run, check, value, bound, near=None, kink=None, knocked=None, control=False, sums=None):
     """run(engine) -> the per-path values (float64); check(got) -> the worst err / bound, asserting the family's rule; value and
-    bound (n,): the model's values and per-path bounds (the power test); near, kink: masks; knocked: the plain direction's mask."""
+    bound (n,): the model's values and per-path bounds (the power test); near, kink: masks; knocked: the plain direction's mask;
+    sums(engine) -> the run form's Estimate of the same call (local vol and Heston level)."""
     n = value.size
     z = np.zeros(n, dtype=bool)
     return V(tag=tag, anti=anti, control=control, run=run, check=check, value=value, bound=bound, near=z if near is None else near,
-             kink=z if kink is None else kink, knocked=knocked)
+             kink=z if kink is None else kink, knocked=knocked, sums=sums)
 
 
 def _draw(eng, X):
@@ -329,7 +400,8 @@ def kinds_of(mk):
 
 def cases(family, mk, m, X, eng, mutate=None):
     """Every call on market mk at m dates in precision X.  mutate: "up_as_down" (the barrier's direction read from |gap|) or
-    "no_compensator" (Merton); every other mutation of the power test is a change of the market itself."""
+    "no_compensator" (Merton), or a name of localvol_ref.MUTATIONS / heston_level_ref.MUTATIONS (those two families); every other
+    mutation of the power test is a change of the market itself."""
     return list(globals()["_" + family + "_cases"](mk, m, X, eng, mutate))
 
 
@@ -447,6 +519,62 @@ def _american_cases(mk, m, X, eng, mutate):
                     P.value, P.bound, near=P.near)
 
 
+def lv_barriers(mk):
+    """(barrier, kind) of a local-vol market: its own barrier with its side's two kinds, the second barrier with the other side's."""
+    own = kinds_of(mk)
+    return [(mk["B"], k) for k in own] + [(mk["B2"], k) for k in lv.KINDS if k not in own]
+
+
+def _localvol_cases(mk, shape, X, eng, mutate):
+    """mutate: one of localvol_ref.MUTATIONS, or "up_as_down" (dk = sgn |ln(B / s)|: a down barrier read as an up barrier)."""
+    o, first, n, tol = mk["o"], mk["first"], N_PATHS, TOL[X]["pay"]
+    m, nt, spd, nn = shape
+    nd = m // spd
+    surf = surface_of(mk, shape)
+    z = lv.localvol_normals(_draw(eng, X), first, n, m, gr.NPB[X])
+    in_walk = mutate if mutate in ("slice_late", "round_nearest", "no_half", "clamp_n", "date_late") else None
+    in_pay = mutate if mutate in ("one_more", "put_as_call") else None
+    both = lv.walk(o, surf, nd, spd, z, anti=True, tol=tol, table=NPX[X], mutation=in_walk)
+    for anti in (False, True):
+        sides = both if anti else both[:1]
+        for right in ("call", "put"):
+            what = ("localvol", shape, right, anti)
+            value, b = lv.european(sides, right, in_pay), lv.european_bound(sides, right)
+            yield _case(("localvol", shape, "european", right, None, anti), anti,
+                        lambda e, right=right: e.localvol_paths(o, surf, m, n, right, SEED, first, X).astype(np.float64),
+                        lambda got, value=value, b=b, what=what: lv.check(got, value, b, what + ("european",)), value, b,
+                        sums=lambda e, right=right: e.localvol(o, surf, m, n, right, SEED, first, X))
+            value, b = lv.asian(sides, right, in_pay), lv.asian_bound(sides, right)
+            yield _case(("localvol", shape, "asian", right, None, anti), anti,
+                        lambda e, right=right: e.localvol_asian_paths(o, surf, nd, spd, n, right, SEED, first, X).astype(np.float64),
+                        lambda got, value=value, b=b, what=what: lv.check(got, value, b, what + ("asian",)), value, b,
+                        sums=lambda e, right=right: e.localvol_asian(o, surf, nd, spd, n, right, SEED, first, X))
+            for B, kind in lv_barriers(mk):
+                up = kind.startswith("up")
+                read = "up" + kind[kind.index("-"):] if mutate == "up_as_down" else kind
+                parts = [lv._barrier_side(s, B, up, right, True) for s in sides]
+                b = sum(p[3] for p in parts) / len(sides) + tol * np.abs(lv.barrier(sides, B, kind, right))
+                near = np.logical_or.reduce([p[1] for p in parts])
+                yield _case(("localvol", shape, "barrier", right, kind, anti), anti,
+                            lambda e, right=right, B=B, kind=kind: e.localvol_barrier_paths(o, surf, B, nd, spd, n, right, SEED, first, X, kind).astype(np.float64),
+                            lambda got, sides=sides, B=B, kind=kind, right=right, what=what: lv.check_barrier(got, sides, B, kind, right, what)[0],
+                            lv.barrier(sides, B, read, right, in_pay), b, near=near, knocked=~lv._barrier_side(sides[0], B, read.startswith("up"), right, False)[0],
+                            sums=lambda e, right=right, B=B, kind=kind: e.localvol_barrier(o, surf, B, nd, spd, n, right, SEED, first, X, kind))
+
+
+def _heston_level_cases(mk, shape, X, eng, mutate):
+    """mutate: one of heston_level_ref.MUTATIONS (the coarse leg's)."""
+    o, model, first, n, tol = mk["o"], mk["model"], mk["first"], N_PATHS, TOL[X]["pay"]
+    nd, spd = shape
+    z1, z2 = hl.level_normals(_draw(eng, X), first, n, nd * spd, hl.NPB[X])
+    both = hl.walk(o, model, nd, spd, z1, z2, anti=True, mutation=mutate, prec=NPX[X])      # prec: as tests/test_gpu_heston_level.py sets it
+    for anti, level in ((False, hl.plain_of(both)), (True, both)):
+        b, kink = hl.bound(level, tol)
+        yield _case(("heston_level", shape, anti), anti, lambda e: e.heston_level_paths(o, model, nd, spd, n, SEED, first, X).astype(np.float64),
+                    lambda got, level=level, anti=anti: hl.check(got, level, tol, ("heston_level", shape, anti))[0], hl.value(level), b, kink=kink,
+                    sums=lambda e: e.heston_level(o, model, nd, spd, n, SEED, first, X))
+
+
 def _rainbow_cases(mk, m, X, eng, mutate):
     first, n, tol = mk["first"], N_PATHS, TOL[X]["pay"]
     z = rr.rainbow_normals(_draw(eng, X), first, n, mk["n"], m, gr.NPB[X])
@@ -502,7 +630,10 @@ def _abs_ln_s0(family, mk, m):
     if family in MULTI:       # |ln(w_i s_i)| for ln(w_i s_i)
         lv = mk["b"]["w"] * mk["b"]["s"]
         return dict(mk, b=dict(mk["b"], w=np.where(lv < 1, 1.0 / (lv * mk["b"]["s"]), mk["b"]["w"])))
-    return _opt(mk, s=math.exp(abs(math.log(mk["o"]["s"]))))
+    s = math.exp(abs(math.log(mk["o"]["s"])))
+    if family == "localvol":      # x0 = |ln s| alone: dk = sgn ln(B / s) is folded apart from it, so the barriers keep their distance
+        return dict(_opt(mk, s=s), B=mk["B"] * s / mk["o"]["s"], B2=mk["B2"] * s / mk["o"]["s"])
+    return _opt(mk, s=s)
 
 
 def _rate_clamped(family, mk, m):
@@ -539,20 +670,41 @@ def _rows_exchanged(family, mk, m):
     return dict(mk, b=dict(b, s=s, w=w))
 
 
+def _grid_mirrored(family, mk, m):
+    """u0 = y_hi / h for -y_lo / h: the grid [-y_hi, -y_lo] under the same values."""
+    def mirrored(shape):
+        s = surface_of(mk, shape)
+        return dict(s, y_lo=-s["y_hi"], y_hi=-s["y_lo"])
+    return dict(mk, surface=mirrored)
+
+
+def _dt_without_t(family, mk, m):
+    """dt = 1 / m.  Local vol: in r dt, dt / 2 and sqrt(dt) -- the model at t = 1 on the same surface.  Heston level: heston_args' dt,
+    in kdt, ktdt, c1, c2, av and aw, while x0 and the per-date table keep r t -- the model at t = 1 with the rate r t."""
+    if family == "localvol":
+        return _opt(mk, t=1.0)             # the grid is the market's own, frozen: the surface stays
+    return _opt(mk, t=1.0, r=mk["o"]["r"] * mk["o"]["t"])
+
+
 CONSTANT_VOL = ["asian", "barrier", "lookback", "merton", "american"]
 # name -> (the families it applies to, market -> market or None, the `mutate` switch of cases())
 MUTATIONS = {
     "|ln S0| for ln S0": (FAMILIES, _abs_ln_s0, None),
-    "rate clamped at 0": (FAMILIES, _rate_clamped, None),
+    "rate clamped at 0": ([f for f in FAMILIES if f != "heston_level"], _rate_clamped, None),
     "T dropped in the volatility step": (CONSTANT_VOL + MULTI, _t_dropped, None),
     "addend of date j - 1": (CONSTANT_VOL + ["heston_path"] + MULTI, _addend_late, None),
-    "gap's sign from |gap|": (["barrier", "merton", "heston_path", "rainbow"], None, "up_as_down"),
-    "|rho| for rho": (["heston", "heston_path"], lambda f, mk, m: dict(mk, model=dict(mk["model"], rho=abs(mk["model"]["rho"]))), None),
+    "gap's sign from |gap|": (["barrier", "merton", "heston_path", "rainbow", "localvol"], None, "up_as_down"),
+    "|rho| for rho": (["heston", "heston_path", "heston_level"], lambda f, mk, m: dict(mk, model=dict(mk["model"], rho=abs(mk["model"]["rho"]))), None),
     "kappa theta dt with T = 1": (["heston", "heston_path"], lambda f, mk, m: dict(mk, model=dict(mk["model"], theta=mk["model"]["theta"] / mk["o"]["t"])), None),
     "sign of mu_j": (["merton"], lambda f, mk, m: dict(mk, jumps=dict(mk["jumps"], mu_j=-mk["jumps"]["mu_j"])), None),
     "compensator dropped": (["merton"], None, "no_compensator"),
     "initial rows of assets 0 and 1 exchanged": (MULTI, _rows_exchanged, None),
+    "u0 from y_hi (a mirrored grid)": (["localvol"], _grid_mirrored, None),
+    "dt without T (T = 1)": (["localvol", "heston_level"], _dt_without_t, None),
+    "|r| for r": (["heston_level"], lambda f, mk, m: _opt(mk, r=abs(mk["o"]["r"])), None),
 }
+MUTATIONS.update({f"localvol_ref: {name}": (["localvol"], None, name) for name in lv.MUTATIONS})
+MUTATIONS.update({f"heston_level_ref: {name}": (["heston_level"], None, name) for name in hl.MUTATIONS})
 
 
 def moved_share(family, mk, m, name, eng=None):
@@ -581,7 +733,7 @@ def moved_share(family, mk, m, name, eng=None):
 
 def _is_up(family, mk):
     """No down barrier on this market: reading the direction from |gap| changes nothing."""
-    if family == "heston_path":
+    if family in ("heston_path", "localvol"):
         return False              # every market carries both barriers
     if family == "rainbow":
         return all(side for _, _, barriers in mk["contracts"] for side in barriers)
@@ -598,8 +750,10 @@ def old_markets(family):
         return [dict(o=o, first=0) for o in lr.CASES]
     if family == "merton":
         return [dict(o=o, B=B, up=B > o["s"], jumps=jp, first=0) for o, B, jp in mr.CASES + [mr.HEAVY]]
-    if family in ("heston", "heston_path"):
+    if family in ("heston", "heston_path", "heston_level"):
         return [dict(o=o, model=model, B_up=hp.UP, B_down=hp.DOWN, first=0) for _, o, model in hr.CASES]
+    if family == "localvol":      # lv.MKT on the two symmetric grids of tests/test_gpu_localvol.py, one barrier per side
+        return [dict(o=lv.MKT, B=lv.UP, B2=lv.DOWN, up=True, first=0, surface=lambda shape, grid=grid: lv.surface_for(shape, grid)) for grid in (lv.WIDE, lv.NARROW)]
     if family == "american":
         return [dict(o=o, kind=kind, first=0) for kind, o in am.MARKETS.items()]
     if family == "rainbow":
